@@ -2,6 +2,10 @@
 """bench.py — moves-evaluated/sec (M1) and best HardSoftScore@60s (M2) of the MI355X hot path on BASELINE.json's
 CVRP-1000 workload.
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N M1 launches, writes the outputs of the last
+one when `--dump-outputs DIR` is given, and prints the result line.  Everything else below -- the rocprofv3 counter passes of
+the roofline, the CPU baseline, the M2 solve legs and the CVRP-5000 side leg -- runs only with `--full`.
+
 M1.  One bench "step" = ONE persistent-kernel launch (sf_solve_steps) that runs `--ls-steps` local-search steps
 (seeded nearby-list candidate generation -> trial delta score -> LateAcceptance -> AcceptedCount(256) forager ->
 apply) for each of `--replicas` independently seeded searches resident on the GPU (the per-GPU batch of the seed
@@ -130,6 +134,9 @@ M2_PMC_PASSES = [["SQ_INSTS_VALU", "SQ_INSTS_SALU", "SQ_INSTS_LDS", "SQ_INSTS_VM
 # SAME command at one residency and the line scales their per-launch counters by the work ratio (consumed candidates of the parent's
 # timed launches / of the child's): per-candidate instruction and byte counts do not depend on how many replicas share a launch.
 PMC_CHILD_MAX_REPLICAS = 6144
+# --dump-outputs: replicas whose routes and counters are written, drawn once with a fixed seed
+DUMP_SAMPLE = 64
+DUMP_SEED = 20240601
 
 
 def cpu_baseline(problem, seed, warm_steps, timed_steps, budget_s):
@@ -306,6 +313,34 @@ def pmc_collect(argv, warmup, steps, kernel_substr, timeout_s, passes=None, atte
     return out, info
 
 
+def dump_outputs(d, out_dir, suffix=""):
+    """--dump-outputs: what a caller of the timed path receives after its last launch, as float64 .npy files (int64 scores and
+    counters of this size are exact in float64).  Scores of every replica; routes and counters of a fixed, seeded sample of
+    DUMP_SAMPLE replicas (the routes of all 98,304 would be ~0.9 GB).  A route file holds one row per sampled replica: the
+    element ids of each list followed by -1, padded with -2 to the longest row."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = d.n_replicas
+    sample = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+
+    def routes(best):
+        rows = [np.concatenate([np.append(np.asarray(r, dtype=np.float64), -1.0) for r in d.working_lists(0, int(i), best=best)]) for i in sample]
+        w = max(len(r) for r in rows)
+        return np.stack([np.pad(r, (0, w - len(r)), constant_values=-2.0) for r in rows])
+
+    arrays = {
+        "working_scores": d.calculate_score().astype(np.float64),  # [replicas, levels] committed (hard, soft)
+        "best_scores": d.best_scores().astype(np.float64),
+        "sample_replicas": sample.astype(np.float64),
+        "sample_working_routes": routes(False),
+        "sample_best_routes": routes(True),
+        # [sample, 10] in the order of sf_stats: step_count, moves_generated, moves_evaluated, moves_accepted, moves_applied,
+        # score_calculations, moves_not_doable, candidates_scored, sources_scanned, reserved
+        "sample_stats": np.array([list(d.stats(int(i)).values()) for i in sample], dtype=np.float64),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+
+
 def seconds_to_reach(curve, target):
     """First time of `curve` [(seconds, score tuple)] at which the score is >= target (lexicographic), or None."""
     if not curve or not target:
@@ -367,6 +402,12 @@ def main():
                     help="M2 extension leg: wall-clock budget of the tuned configuration (0 = skip); see TUNED below")
     ap.add_argument("--c5-seconds", type=float, default=5.0,
                     help="side leg: seconds of the same 2-leaf search on BASELINE config 5 (CVRP-5000 / 500, 2,816 replicas per GPU; 0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline M1 figure, run the rocprofv3 counter passes (roofline), the CPU baseline, the M2 solve legs and the "
+                         "CVRP-5000 side leg; a plain run does none of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed launches, write what the last one computed (scores, best scores, a fixed sample of replicas' routes "
+                         "and counters) as DIR/<name>.npy in float64")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc child passes (roofline fields stay null)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--pmc-child-out", default=None, help=argparse.SUPPRESS)
@@ -488,6 +529,8 @@ def main():
     delta = {k: after[k] - before[k] for k in after}
     replica0_score = [int(v) for v in d.calculate_score()[0]]
     m1_best = list(max(tuple(int(v) for v in s) for s in d.best_scores()))
+    if args.dump_outputs:
+        dump_outputs(d, args.dump_outputs, "" if world == 1 else f"_rank{rank}")
 
     moves_local = delta["moves_evaluated"]
     scored_local = delta["candidates_scored"]
@@ -498,7 +541,7 @@ def main():
     # ---- M2: a fresh portfolio solves for --solve-seconds of wall clock; the CPU oracle beside it on a host core ----
     solve = None
     dx = d  # the context whose best score goes into the portfolio exchange
-    if args.solve_seconds > 0:
+    if args.full and args.solve_seconds > 0:
         d.close()
         prob2 = problem if args.solve_start == "roundrobin" else dict(problem, routes=[[] for _ in problem["routes"]])
         m2_leaves = M2_POLICIES[args.solve_policy]
@@ -554,7 +597,7 @@ def main():
 
     # ---- M2 extension leg: the tuned configuration (TUNED), elite migration on; the CPU oracle with the same configuration beside it ----
     tuned = None
-    if args.tuned_seconds > 0 and args.solve_seconds > 0:
+    if args.full and args.tuned_seconds > 0 and args.solve_seconds > 0:
         prob3 = problem if args.solve_start == "roundrobin" else dict(problem, routes=[[] for _ in problem["routes"]])
         d3 = new_director(prob3, TUNED["leaves"], TUNED["replicas"], TUNED["late_acceptance_size"], TUNED["accepted_count_limit"])
         d3.calculate_score()
@@ -599,7 +642,7 @@ def main():
 
     # ---- side leg: BASELINE config 5 (CVRP-5000 / 500 vehicles, the size an 8-GPU portfolio runs), the same 2-leaf search for a few seconds ----
     c5 = None
-    if args.c5_seconds > 0 and args.solve_seconds > 0 and args.customers != 5000 and not args.pmc_child:
+    if args.full and args.c5_seconds > 0 and args.solve_seconds > 0 and args.customers != 5000 and not args.pmc_child:
         try:
             prob5 = datasets.make_cvrp(5000, 500, 55, seed=args.seed)
             d5 = sfa.build_cvrp(prob5, n_replicas=C5_REPLICAS, device_id=local_rank, leaves=("nearby_change", "nearby_swap"))
@@ -706,18 +749,21 @@ def main():
         kernel = "k_list_search_wave" if engine == "wave" else "k_list_search"
         # ---- PMC: rocprofv3 child passes of this command (N = 1 only: one GPU, one process) ----
         pmc, pmc_info, pmc_source, pmc_full, pmc_child_raw = None, {}, None, None, None
+        if not args.full:
+            pmc_source = "not collected: the counter passes run with --full"
         child_argv = ["--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup), "--replicas", str(min(args.replicas, PMC_CHILD_MAX_REPLICAS)),
                       "--ls-steps", str(args.ls_steps), "--customers", str(args.customers), "--vehicles", str(args.vehicles),
                       "--capacity", str(args.capacity), "--seed", str(args.seed), "--engine", args.engine]
         # the CPU baseline leg (one host core, ~20 s) runs on a QUIET host, before the counter passes start their own processes (round 5 ran it
         # beside them: contention could only lower the baseline and inflate gpu_over_cpu); an exception becomes a field of the line, not its loss
         cb_box = {}
-        if not args.no_cpu_baseline:
+        cpu_leg = args.full and not args.no_cpu_baseline
+        if cpu_leg:
             try:
                 cb_box["result"] = cpu_baseline(problem, args.seed, args.warmup * args.ls_steps, args.steps * args.ls_steps, args.cpu_seconds)
             except Exception as e:
                 cb_box["result"] = {"error": repr(e)}
-        if world == 1 and not args.no_pmc:
+        if world == 1 and args.full and not args.no_pmc:
             pmc, pmc_info = pmc_collect(child_argv, args.warmup, args.steps, kernel + "<", timeout_s=40, attempts=3)
             if pmc is not None and args.replicas > PMC_CHILD_MAX_REPLICAS:
                 # the per-candidate counts the scaling below assumes, checked on the parent's own launch shape: a two-counter pass survives
@@ -935,7 +981,7 @@ def main():
             side["cvrp5000_nearby2"] = c5
         if side:
             out["extra"]["side_configs"] = side
-        if not args.no_cpu_baseline:
+        if cpu_leg:
             cb = cb_box["result"]
             out["cpu_baseline"] = cb
             if "error" not in cb:

@@ -3,7 +3,7 @@ R=$GRAFT_REPO_ROOT; cd $R; O=$R/gpurun_out/r05_final; mkdir -p $O
 timeout 1800 python -m pytest tests -q -m gpu 2>&1 | grep -E "passed|failed|error|Error" | tee $O/gpu_tests.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee -a $O/gpu_tests.txt
 timeout 400 python scripts/fuzz_parity.py 240 21000 > $O/fuzz_parity.json 2> $O/fuzz_parity.err; tail -c 400 $O/fuzz_parity.json; echo
-timeout 1200 python bench.py > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err
+timeout 1200 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err
 python - <<PY
 import json
 d=json.loads(open("$O/bench.json").read().strip().splitlines()[-1]); r=d["roofline"]

@@ -3,7 +3,7 @@
 # counter profile of the precedence kernel (50 x 20 nine-leaf) on the library that ships
 R=$GRAFT_REPO_ROOT; cd $R; O=$R/gpurun_out/r06_r11; mkdir -p $O; export TMPDIR=/tmp
 export SF_COMMIT=$(cat $R/build/commit.txt 2>/dev/null)  # (.git does not travel: the container writes HEAD there before the call)
-timeout 600 python bench.py --steps 20 --warmup 5 --solve-seconds 20 --tuned-seconds 0 --c5-seconds 3 2>$O/bench.err | tail -1 > $O/bench_short.json
+timeout 600 python bench.py --full --steps 20 --warmup 5 --solve-seconds 20 --tuned-seconds 0 --c5-seconds 3 2>$O/bench.err | tail -1 > $O/bench_short.json
 python - <<'P' | tee $O/bench_short_summary.txt
 import json,os
 d=json.loads(open(os.environ['GRAFT_REPO_ROOT']+'/gpurun_out/r06_r11/bench_short.json').read())

@@ -12,7 +12,7 @@ done
 for rep in 3072 6144 12288; do
   echo "c2 la replicas $rep: $(timeout 300 python scripts/graph_bench.py $rep 100 10 la 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['gpu_moves_per_s']/1e9,3),'G', d['kernel_ms_per_launch'], d.get('replica0_matches_indexed_cpu'))")" | tee -a $O/shapes.txt
 done
-timeout 900 python bench.py --steps 20 --warmup 5 2>$O/bench.err | tail -1 > $O/bench.json
+timeout 900 python bench.py --full --steps 20 --warmup 5 2>$O/bench.err | tail -1 > $O/bench.json
 python - <<'P' | tee $O/bench_summary.txt
 import json,os
 d=json.loads(open(os.environ['GRAFT_REPO_ROOT']+'/gpurun_out/r06_r14/bench.json').read())

@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 6, twenty-fifth GPU call: do the M2 leg's counter passes survive launches of 24,576 replicas of k_mixed_search_wave?
 R=$GRAFT_REPO_ROOT; cd $R; O=$R/gpurun_out/r06_r25; mkdir -p $O; export TMPDIR=/tmp
-timeout 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --tuned-seconds 0 --c5-seconds 0 --solve-seconds 30 --solve-replicas 24576 2>$O/err.txt | tail -1 > $O/bench.json
+timeout 600 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --tuned-seconds 0 --c5-seconds 0 --solve-seconds 30 --solve-replicas 24576 2>$O/err.txt | tail -1 > $O/bench.json
 python - <<'P' | tee $O/summary.txt
 import json,os
 d=json.loads(open(os.environ['GRAFT_REPO_ROOT']+'/gpurun_out/r06_r25/bench.json').read())

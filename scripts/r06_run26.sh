@@ -6,7 +6,7 @@ export SF_COMMIT=$(cat $R/build/commit.txt 2>/dev/null)
 timeout 600 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 | tee $O/smoke.txt
 timeout 1800 python -m pytest tests -x -q -m gpu 2>&1 | grep -E "passed|failed|error|Error" | tail -5 | tee $O/tests.txt
 for fam in cvrp jobshop precedence; do SF_FUZZ_MODEL=$fam timeout 200 python scripts/fuzz_parity.py 90 66000 > $O/fuzz_$fam.json 2>> $O/fuzz.err; tail -c 160 $O/fuzz_$fam.json; echo; done
-timeout 900 python bench.py --steps 20 --warmup 5 2>$O/bench.err | tail -1 > $O/bench.json
+timeout 900 python bench.py --full --steps 20 --warmup 5 2>$O/bench.err | tail -1 > $O/bench.json
 python - <<'P' | tee $O/bench_summary.txt
 import json,os
 d=json.loads(open(os.environ['GRAFT_REPO_ROOT']+'/gpurun_out/r06_r26/bench.json').read())

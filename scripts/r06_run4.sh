@@ -3,7 +3,7 @@
 # LATE M2 regime (what the driver's 60 s leg prices)
 R=$GRAFT_REPO_ROOT; cd $R; O=$R/gpurun_out/r06_r4; mkdir -p $O; export TMPDIR=/tmp
 timeout 1200 python -m pytest tests/test_gpu_cvrp.py tests/test_gpu_budget.py tests/test_gpu_foragers.py tests/test_gpu_mixed.py -x -q -m gpu 2>&1 | grep -E "passed|failed|error" | tail -3 | tee $O/tests.txt
-B="python bench.py --no-pmc --solve-seconds 0 --steps 20 --warmup 5"
+B="python bench.py --full --no-pmc --solve-seconds 0 --steps 20 --warmup 5"
 for lib in solverforge_amd/libsolverforge_amd.so build/libsf_wave_base.so solverforge_amd/libsolverforge_amd.so; do
   SF_AMD_LIB=$R/$lib timeout 300 $B 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$lib', round(d['value']/1e9,2), round(d['roofline']['avg_launch_ms'],3), d['extra'].get('replica0_matches_cpu_oracle'))" | tee -a $O/ab.txt
 done

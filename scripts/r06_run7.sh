@@ -11,4 +11,4 @@ C5="python bench.py --customers 5000 --vehicles 500 --replicas 2816 --ls-steps 1
 for lib in build/libsf_wbase.so solverforge_amd/libsolverforge_amd.so; do
   SF_AMD_LIB=$R/$lib timeout 300 $C5 --no-pmc 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('c5 $lib', round(d['value']/1e9,2), round(d['roofline']['avg_launch_ms'],3))" | tee -a $O/ab.txt
 done
-timeout 900 $C5 2>$O/c5.err | tail -1 > $O/c5_bench.json; cut -c1-1500 $O/c5_bench.json
+timeout 900 $C5 --full 2>$O/c5.err | tail -1 > $O/c5_bench.json; cut -c1-1500 $O/c5_bench.json

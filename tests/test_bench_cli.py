@@ -73,3 +73,39 @@ def test_launch_shapes_are_whole_residencies():
     assert b.PMC_CHILD_MAX_REPLICAS % (24 * 256) == 0
     assert 0 < b.M2_PMC_TIMED <= b.M2_PMC_WARM  # the window [WARM, WARM + TIMED) of launches: past the construction, a few launches long
     assert [c for p in b.M2_PMC_PASSES for c in p].count("SQ_INSTS_SALU") == 1
+
+
+def test_full_and_dump_outputs_are_options():
+    """The side legs sit behind --full (off by default); --dump-outputs DIR is accepted."""
+    r = _run(["--help"])
+    assert r.returncode == 0
+    assert b"--full" in r.stdout and b"--dump-outputs" in r.stdout
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_identical_outputs(tmp_path):
+    """A plain run times only the M1 launches (no CPU baseline, no M2 legs) and, with --dump-outputs, writes the last launch's
+    outputs as float64 .npy files; two runs with the same arguments write the same arrays."""
+    import json
+
+    import numpy as np
+
+    args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--replicas", "512", "--ls-steps", "50"]
+    lines = []
+    for k in range(2):
+        r = _run(args + ["--dump-outputs", str(tmp_path / f"run{k}")])
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.decode().strip().splitlines()[-1]))
+    for line in lines:
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert "cpu_baseline" not in line and "best_score_at_60s" not in line["extra"] and "side_configs" not in line["extra"]
+    names = sorted(os.listdir(tmp_path / "run0"))
+    assert names == sorted(os.listdir(tmp_path / "run1")) and "working_scores.npy" in names
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "run0" / n), np.load(tmp_path / "run1" / n)
+        assert a.dtype == np.float64 and np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    scores = np.load(tmp_path / "run0" / "working_scores.npy")
+    assert scores.shape == (512, 2) and scores[0].tolist() == lines[0]["extra"]["replica0_working_score"]
