@@ -195,7 +195,8 @@ typedef enum sf_constraint_kind {
  * SF_C_CROSS_QUEENS = {COL_NE(column)} and {VALUE_EQ or VALUE_ABSDIFF_EQ_COL(column)}  (examples/scalar-graph-coloring/src/domain/
  * graph_coloring.rs:28-41, examples/mixed-job-shop/src/domain/job_shop_plan.rs:50-62, examples/nqueens/src/domain/board.rs:30-44).
  * On the device a clause that is one CSR_CONTAINS or one COL_EQ term becomes the partner index the trial walks (deg(e) tests instead of n);
- * the remaining clauses are interpreted per candidate pair from the kernel's argument block (wave-uniform control, per-lane data). */
+ * the remaining clauses are interpreted per candidate pair from the kernel's argument block (wave-uniform control, per-lane data).
+ * The presets and the programs count together against the limit of SF_MAX_PAIR_JOINS = 4 predicate joins per scalar class. */
 typedef enum sf_pair_op {
     SF_PAIR_VALUE_EQ = 1,             /* left.value == right.value */
     SF_PAIR_VALUE_NE = 2,             /* left.value != right.value */
@@ -218,8 +219,10 @@ typedef struct sf_pair_term {
 } sf_pair_term;
 /* for_each(E).join(for_each(E), predicate).penalize(weight) on the scalar class `descriptor_index`: every pair left.id < right.id of
  * ASSIGNED entities for which the program holds costs `weight` on `level` (IncrementalBiConstraint over a predicate join:
- * constraint/cross_bi_incremental/{state,incremental}.rs).  One predicate join per scalar class; <= 8 terms, of which <= 6 remain after
- * the partner index took its clause.  SF_ERR_INVALID for malformed programs / facts, SF_ERR_UNSUPPORTED beyond the limits. */
+ * constraint/cross_bi_incremental/{state,incremental}.rs).  Up to SF_MAX_PAIR_JOINS = 4 predicate joins per scalar class -- programs and
+ * the three presets in any mix, each with its own level and weight (levels may be shared); sf_evaluate_each reports one row per join, in
+ * declaration order; a fifth join is SF_ERR_UNSUPPORTED at sf_initialize.  Each program: <= 8 terms, of which <= 6 remain after the
+ * partner index took its clause.  SF_ERR_INVALID for malformed programs / facts, SF_ERR_UNSUPPORTED beyond the limits. */
 int32_t sf_constraint_add_pair_join(sf_ctx* ctx, int32_t descriptor_index, int32_t variable_index, const sf_pair_term* terms, int32_t n_terms,
                                     int32_t level, int64_t weight);
 

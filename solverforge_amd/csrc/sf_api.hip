@@ -1403,6 +1403,7 @@ int32_t sf_evaluate_each(sf_ctx* ctx, int32_t replica, int64_t* out_scores, int6
         return false;
     };
     size_t i = 0;
+    int join_ordinal = 0;  // predicate joins of the scalar class, in declaration order: a class with several keeps one aggregate word each
     for (auto& cs : ctx->constraints) {
         int64_t raw = 0, count = 0;
         const bool on_list = ctx->has_list_model && cs.desc == ctx->list_desc;
@@ -1421,7 +1422,10 @@ int32_t sf_evaluate_each(sf_ctx* ctx, int32_t replica, int64_t* out_scores, int6
             case SF_C_CROSS_ADJACENT_EQUAL:
             case SF_C_CROSS_GROUP_EQUAL:
             case SF_C_PAIR_JOIN_:
-            case SF_C_CROSS_QUEENS: raw = q[4], count = q[4]; break;
+            case SF_C_CROSS_QUEENS:
+                raw = ctx->sm.n_xj > 0 ? q[SF_EACH_XJ + join_ordinal] : q[4], count = raw;
+                ++join_ordinal;
+                break;
             case SF_C_CROSS_OWNER_MATCH: raw = q[17], count = q[17]; break;
             case SF_C_SELFJOIN_VALUE_EQUAL: raw = q[5], count = q[5]; break;
             case SF_C_GROUPED_VALUE_SUM:

@@ -186,6 +186,110 @@ static int compile_uni_programs(sf_ctx* ctx, int d, ScalarModel& m) {
     return SF_OK;
 }
 
+// One predicate join of a scalar class (sf_constraint_add_pair_join, or one of the three presets) compiled into one join record: the program, the
+// clause that drives the partner index (built on the host from a CSR or a group column), the residual program, and the specialised loop the
+// kernels run for it, if one matches (SF_AMD_IR_INTERPRET=1: always interpret).
+static int compile_pair_join(sf_ctx* ctx, int n, const ConstraintSpec& cs, PairJoin& j) {
+    j = PairJoin{SC_NONE, cs.level, cs.weight, nullptr, nullptr, nullptr, nullptr, 0, 0};
+    int rc;
+    std::vector<sf_pair_term> prog = cs.terms;
+    if (cs.kind == SF_C_CROSS_ADJACENT_EQUAL)
+        prog = {{SF_PAIR_CSR_CONTAINS, 0, cs.fact, -1, 0}, {SF_PAIR_VALUE_EQ, 1, -1, -1, 0}};
+    else if (cs.kind == SF_C_CROSS_GROUP_EQUAL)
+        prog = {{SF_PAIR_COL_EQ, 0, cs.fact, -1, 0}, {SF_PAIR_VALUE_EQ, 1, -1, -1, 0}};
+    else if (cs.kind == SF_C_CROSS_QUEENS)
+        prog = {{SF_PAIR_COL_NE, 0, cs.fact, -1, 0}, {SF_PAIR_VALUE_EQ, 1, -1, -1, 0}, {SF_PAIR_VALUE_ABSDIFF_EQ_COL, 1, cs.fact, -1, 0}};
+    // facts of every term
+    auto col_fact = [&](int id) -> const int32_t* {
+        if (!ctx->facts.count(id) || ctx->facts[id].type != 2 || ctx->facts[id].rows < n) return nullptr;
+        return (const int32_t*)ctx->facts[id].d0;
+    };
+    for (auto& pt : prog) {
+        if (pt.op == SF_PAIR_CSR_CONTAINS) {
+            if (!ctx->facts.count(pt.fact) || ctx->facts[pt.fact].type != 4 || ctx->facts[pt.fact].rows != n)
+                return fail(ctx, SF_ERR_INVALID, "pair join: CSR_CONTAINS needs a CSR fact with one row per entity");
+        } else if (pt.op == SF_PAIR_TABLE_NONZERO) {
+            if (!ctx->facts.count(pt.fact) || ctx->facts[pt.fact].type != 1 || !col_fact(pt.fact_b))
+                return fail(ctx, SF_ERR_INVALID, "pair join: TABLE_NONZERO needs an i64 matrix and an i32 key column");
+            std::vector<int32_t> key((size_t)n);
+            HIPCHK(ctx, hipMemcpy(key.data(), col_fact(pt.fact_b), key.size() * 4, hipMemcpyDeviceToHost));
+            for (int32_t k : key)
+                if (k < 0 || k >= ctx->facts[pt.fact].rows || k >= ctx->facts[pt.fact].cols) return fail(ctx, SF_ERR_INVALID, "pair join: table key out of range");
+        } else if (pt.op != SF_PAIR_VALUE_EQ && pt.op != SF_PAIR_VALUE_NE && pt.op != SF_PAIR_VALUE_ABSDIFF_LE) {
+            if (!col_fact(pt.fact)) return fail(ctx, SF_ERR_INVALID, "pair join: the op needs an i32 column with one entry per entity");
+        }
+    }
+    // the clause that drives the partner index: a clause of exactly one CSR_CONTAINS term, else of exactly one COL_EQ term
+    std::map<int, int> clause_size;
+    for (auto& pt : prog) clause_size[pt.clause] += 1;
+    int driver = -1;
+    for (int want : {(int)SF_PAIR_CSR_CONTAINS, (int)SF_PAIR_COL_EQ})
+        for (size_t t = 0; t < prog.size() && driver < 0; ++t)
+            if (prog[t].op == want && clause_size[prog[t].clause] == 1) driver = (int)t;
+    if (driver >= 0) {
+        std::vector<uint32_t> poff, pn;
+        if (prog[(size_t)driver].op == SF_PAIR_CSR_CONTAINS) {
+            Fact& f = ctx->facts[prog[(size_t)driver].fact];
+            std::vector<uint32_t> off((size_t)n + 1), adj((size_t)f.cols);
+            HIPCHK(ctx, hipMemcpy(off.data(), f.d0, off.size() * 4, hipMemcpyDeviceToHost));
+            if (f.cols) HIPCHK(ctx, hipMemcpy(adj.data(), f.d1, adj.size() * 4, hipMemcpyDeviceToHost));
+            partners_from_adjacency(n, off, adj, poff, pn);
+        } else {
+            std::vector<int32_t> group((size_t)n);
+            HIPCHK(ctx, hipMemcpy(group.data(), col_fact(prog[(size_t)driver].fact), group.size() * 4, hipMemcpyDeviceToHost));
+            partners_from_groups(n, group, poff, pn);
+        }
+        uint32_t *d_off = nullptr, *d_pn = nullptr;
+        if ((rc = upload(ctx, &d_off, poff.data(), poff.size()))) return rc;
+        if ((rc = upload(ctx, &d_pn, pn.data(), pn.size()))) return rc;
+        j.pn_off = d_off;
+        j.pn = d_pn;
+    }
+    std::vector<sf_pair_term> rest;
+    for (size_t t = 0; t < prog.size(); ++t)
+        if ((int)t != driver) rest.push_back(prog[t]);
+    if ((int)rest.size() > SF_IR_MAX) return fail(ctx, SF_ERR_UNSUPPORTED, "pair join: more than six terms left after the partner index took its clause");
+    // specialisations of the interpreter for the two programs of the reference's examples (SF_AMD_IR_INTERPRET=1: always interpret)
+    const char* ie = std::getenv("SF_AMD_IR_INTERPRET");
+    const bool interpret = ie && std::atoi(ie) != 0;
+    const bool only_value_eq = rest.size() == 1 && rest[0].op == SF_PAIR_VALUE_EQ;
+    const bool queens = driver < 0 && rest.size() == 3 && rest[0].op == SF_PAIR_COL_NE && rest[1].op == SF_PAIR_VALUE_EQ &&
+                        rest[2].op == SF_PAIR_VALUE_ABSDIFF_EQ_COL && rest[1].clause == rest[2].clause && rest[0].clause != rest[1].clause &&
+                        rest[0].fact == rest[2].fact;
+    if (driver >= 0 && only_value_eq && !interpret) {
+        j.kind = SC_PARTNERS_EQUAL;
+    } else if (queens && !interpret) {
+        j.col = col_fact(rest[0].fact);
+        j.kind = SC_QUEENS;
+    } else {
+        std::vector<PairTerm> dev(rest.size());
+        for (size_t t = 0; t < rest.size(); ++t) {
+            const sf_pair_term& pt = rest[t];
+            PairTerm& q = dev[t];
+            q.op_clause = pt.op | (pt.clause << 8);
+            q.cols = 0;
+            q.param = pt.param;
+            q.col = nullptr, q.coff = nullptr, q.cval = nullptr, q.table = nullptr;
+            if (pt.op == SF_PAIR_CSR_CONTAINS) {
+                q.coff = (const uint32_t*)ctx->facts[pt.fact].d0;
+                q.cval = (const uint32_t*)ctx->facts[pt.fact].d1;
+            } else if (pt.op == SF_PAIR_TABLE_NONZERO) {
+                q.table = (const int64_t*)ctx->facts[pt.fact].d0;
+                q.cols = ctx->facts[pt.fact].cols;
+                q.col = col_fact(pt.fact_b);
+            } else if (pt.fact >= 0) {
+                q.col = col_fact(pt.fact);
+            }
+        }
+        PairTerm* d_ir = nullptr;
+        if ((rc = upload(ctx, &d_ir, dev.data(), dev.size()))) return rc;
+        j.ir = d_ir;
+        j.ir_n = (int32_t)dev.size();
+        j.kind = driver >= 0 ? SC_IR_PARTNERS : SC_IR_DENSE;
+    }
+    return SF_OK;
+}
+
 static int build_scalar_model(sf_ctx* ctx, int d) {
     ClassSpec& c = ctx->classes[d];
     ScalarModel& m = ctx->sm;
@@ -200,6 +304,7 @@ static int build_scalar_model(sf_ctx* ctx, int d) {
     for (int32_t v : c.scalar_init)
         if (v < -1 || v >= m.n_values) return fail(ctx, SF_ERR_INVALID, "initial scalar value out of range");
     int rc;
+    std::vector<PairJoin> joins;  // the predicate joins of the class, in declaration order
     for (auto& cs : ctx->constraints) {
         if (cs.desc != d) continue;
         if (cs.kind == SF_C_UNI_UNASSIGNED) {
@@ -213,104 +318,9 @@ static int build_scalar_model(sf_ctx* ctx, int d) {
         } else if (cs.kind == SF_C_CROSS_ADJACENT_EQUAL || cs.kind == SF_C_CROSS_GROUP_EQUAL || cs.kind == SF_C_CROSS_QUEENS || cs.kind == SF_C_PAIR_JOIN_) {
             // One compile path for every predicate join: the three model-shaped kinds are PRESETS of the pair-predicate program
             // (include/solverforge_amd.h, sf_pair_term).
-            if (m.cross_level >= 0) return fail(ctx, SF_ERR_UNSUPPORTED, "one predicate join per scalar class");
-            std::vector<sf_pair_term> prog = cs.terms;
-            if (cs.kind == SF_C_CROSS_ADJACENT_EQUAL)
-                prog = {{SF_PAIR_CSR_CONTAINS, 0, cs.fact, -1, 0}, {SF_PAIR_VALUE_EQ, 1, -1, -1, 0}};
-            else if (cs.kind == SF_C_CROSS_GROUP_EQUAL)
-                prog = {{SF_PAIR_COL_EQ, 0, cs.fact, -1, 0}, {SF_PAIR_VALUE_EQ, 1, -1, -1, 0}};
-            else if (cs.kind == SF_C_CROSS_QUEENS)
-                prog = {{SF_PAIR_COL_NE, 0, cs.fact, -1, 0}, {SF_PAIR_VALUE_EQ, 1, -1, -1, 0}, {SF_PAIR_VALUE_ABSDIFF_EQ_COL, 1, cs.fact, -1, 0}};
-            // facts of every term
-            auto col_fact = [&](int id) -> const int32_t* {
-                if (!ctx->facts.count(id) || ctx->facts[id].type != 2 || ctx->facts[id].rows < m.n) return nullptr;
-                return (const int32_t*)ctx->facts[id].d0;
-            };
-            for (auto& pt : prog) {
-                if (pt.op == SF_PAIR_CSR_CONTAINS) {
-                    if (!ctx->facts.count(pt.fact) || ctx->facts[pt.fact].type != 4 || ctx->facts[pt.fact].rows != m.n)
-                        return fail(ctx, SF_ERR_INVALID, "pair join: CSR_CONTAINS needs a CSR fact with one row per entity");
-                } else if (pt.op == SF_PAIR_TABLE_NONZERO) {
-                    if (!ctx->facts.count(pt.fact) || ctx->facts[pt.fact].type != 1 || !col_fact(pt.fact_b))
-                        return fail(ctx, SF_ERR_INVALID, "pair join: TABLE_NONZERO needs an i64 matrix and an i32 key column");
-                    std::vector<int32_t> key((size_t)m.n);
-                    HIPCHK(ctx, hipMemcpy(key.data(), col_fact(pt.fact_b), key.size() * 4, hipMemcpyDeviceToHost));
-                    for (int32_t k : key)
-                        if (k < 0 || k >= ctx->facts[pt.fact].rows || k >= ctx->facts[pt.fact].cols) return fail(ctx, SF_ERR_INVALID, "pair join: table key out of range");
-                } else if (pt.op != SF_PAIR_VALUE_EQ && pt.op != SF_PAIR_VALUE_NE && pt.op != SF_PAIR_VALUE_ABSDIFF_LE) {
-                    if (!col_fact(pt.fact)) return fail(ctx, SF_ERR_INVALID, "pair join: the op needs an i32 column with one entry per entity");
-                }
-            }
-            // the clause that drives the partner index: a clause of exactly one CSR_CONTAINS term, else of exactly one COL_EQ term
-            std::map<int, int> clause_size;
-            for (auto& pt : prog) clause_size[pt.clause] += 1;
-            int driver = -1;
-            for (int want : {(int)SF_PAIR_CSR_CONTAINS, (int)SF_PAIR_COL_EQ})
-                for (size_t t = 0; t < prog.size() && driver < 0; ++t)
-                    if (prog[t].op == want && clause_size[prog[t].clause] == 1) driver = (int)t;
-            if (driver >= 0) {
-                std::vector<uint32_t> poff, pn;
-                if (prog[(size_t)driver].op == SF_PAIR_CSR_CONTAINS) {
-                    Fact& f = ctx->facts[prog[(size_t)driver].fact];
-                    std::vector<uint32_t> off((size_t)m.n + 1), adj((size_t)f.cols);
-                    HIPCHK(ctx, hipMemcpy(off.data(), f.d0, off.size() * 4, hipMemcpyDeviceToHost));
-                    if (f.cols) HIPCHK(ctx, hipMemcpy(adj.data(), f.d1, adj.size() * 4, hipMemcpyDeviceToHost));
-                    partners_from_adjacency(m.n, off, adj, poff, pn);
-                } else {
-                    std::vector<int32_t> group((size_t)m.n);
-                    HIPCHK(ctx, hipMemcpy(group.data(), col_fact(prog[(size_t)driver].fact), group.size() * 4, hipMemcpyDeviceToHost));
-                    partners_from_groups(m.n, group, poff, pn);
-                }
-                uint32_t *d_off = nullptr, *d_pn = nullptr;
-                if ((rc = upload(ctx, &d_off, poff.data(), poff.size()))) return rc;
-                if ((rc = upload(ctx, &d_pn, pn.data(), pn.size()))) return rc;
-                m.pn_off = d_off;
-                m.pn = d_pn;
-            }
-            std::vector<sf_pair_term> rest;
-            for (size_t t = 0; t < prog.size(); ++t)
-                if ((int)t != driver) rest.push_back(prog[t]);
-            if ((int)rest.size() > SF_IR_MAX) return fail(ctx, SF_ERR_UNSUPPORTED, "pair join: more than six terms left after the partner index took its clause");
-            // specialisations of the interpreter for the two programs of the reference's examples (SF_AMD_IR_INTERPRET=1: always interpret)
-            const char* ie = std::getenv("SF_AMD_IR_INTERPRET");
-            const bool interpret = ie && std::atoi(ie) != 0;
-            const bool only_value_eq = rest.size() == 1 && rest[0].op == SF_PAIR_VALUE_EQ;
-            const bool queens = driver < 0 && rest.size() == 3 && rest[0].op == SF_PAIR_COL_NE && rest[1].op == SF_PAIR_VALUE_EQ &&
-                                rest[2].op == SF_PAIR_VALUE_ABSDIFF_EQ_COL && rest[1].clause == rest[2].clause && rest[0].clause != rest[1].clause &&
-                                rest[0].fact == rest[2].fact;
-            if (driver >= 0 && only_value_eq && !interpret) {
-                m.cross_kind = SC_PARTNERS_EQUAL;
-            } else if (queens && !interpret) {
-                m.col = col_fact(rest[0].fact);
-                m.cross_kind = SC_QUEENS;
-            } else {
-                std::vector<PairTerm> dev(rest.size());
-                for (size_t t = 0; t < rest.size(); ++t) {
-                    const sf_pair_term& pt = rest[t];
-                    PairTerm& q = dev[t];
-                    q.op_clause = pt.op | (pt.clause << 8);
-                    q.cols = 0;
-                    q.param = pt.param;
-                    q.col = nullptr, q.coff = nullptr, q.cval = nullptr, q.table = nullptr;
-                    if (pt.op == SF_PAIR_CSR_CONTAINS) {
-                        q.coff = (const uint32_t*)ctx->facts[pt.fact].d0;
-                        q.cval = (const uint32_t*)ctx->facts[pt.fact].d1;
-                    } else if (pt.op == SF_PAIR_TABLE_NONZERO) {
-                        q.table = (const int64_t*)ctx->facts[pt.fact].d0;
-                        q.cols = ctx->facts[pt.fact].cols;
-                        q.col = col_fact(pt.fact_b);
-                    } else if (pt.fact >= 0) {
-                        q.col = col_fact(pt.fact);
-                    }
-                }
-                PairTerm* d_ir = nullptr;
-                if ((rc = upload(ctx, &d_ir, dev.data(), dev.size()))) return rc;
-                m.ir = d_ir;
-                m.ir_n = (int32_t)dev.size();
-                m.cross_kind = driver >= 0 ? SC_IR_PARTNERS : SC_IR_DENSE;
-            }
-            m.cross_level = cs.level;
-            m.cross_weight = cs.weight;
+            if ((int)joins.size() >= SF_MAX_PAIR_JOINS) return fail(ctx, SF_ERR_UNSUPPORTED, "more than SF_MAX_PAIR_JOINS = 4 predicate joins per scalar class");
+            joins.emplace_back();
+            if ((rc = compile_pair_join(ctx, m.n, cs, joins.back()))) return rc;
         } else if (cs.kind == SF_C_SELFJOIN_VALUE_EQUAL) {
             if (cs.param != 0 && (cs.param < 2 || cs.param > 5)) return fail(ctx, SF_ERR_INVALID, "self-join arity must be 2..5");
             m.sj_level = cs.level;
@@ -418,6 +428,16 @@ static int build_scalar_model(sf_ctx* ctx, int d) {
         } else
             return fail(ctx, SF_ERR_UNSUPPORTED, "constraint kind on a scalar class");
     }
+    if (joins.size() == 1) {  // one join: the class's own join fields, as the kernels of the single-join classes read them
+        const PairJoin& j = joins[0];
+        m.cross_kind = j.kind, m.cross_level = j.level, m.cross_weight = j.weight;
+        m.pn_off = j.pn_off, m.pn = j.pn, m.col = j.col, m.ir = j.ir, m.ir_n = j.ir_n;
+    } else if (joins.size() > 1) {  // several: all of them in the device array of join records (scalar unit 2), the own fields unused
+        PairJoin* d_xj = nullptr;
+        if ((rc = upload(ctx, &d_xj, joins.data(), joins.size()))) return rc;
+        m.xj = d_xj;
+        m.n_xj = (int32_t)joins.size();
+    }
     if ((rc = compile_uni_programs(ctx, d, m))) return rc;
     if (!c.value_off.empty()) {
         uint32_t* d_off = nullptr;
@@ -457,8 +477,11 @@ static int launch_scalar_search_t(sf_ctx* ctx, const SearchParams& p, int n_repl
     if (lds > SF_LDS_BUDGET) return fail(ctx, SF_ERR_UNSUPPORTED, "scalar class does not fit the LDS slices of one workgroup");
     SearchParams q = p;
     q.n_launch = n_replicas;
-    // the unit with the interpreted joins only for the models that need them (SC_IR_*): the specialised kernels do not carry the interpreter
-    if (ctx->sm.cross_kind == SC_IR_PARTNERS || ctx->sm.cross_kind == SC_IR_DENSE)
+    // the unit with the interpreted joins only for the models that need them (SC_IR_*): the specialised kernels do not carry the interpreter;
+    // the classes with several joins take the unit with the loop over their join records
+    if (ctx->sm.n_xj > 0)
+        HIPCHK(ctx, (launch_tu_scalar<L, (int)sizeof(VT), 2>(trace, make_launch(ctx, &q, (n_replicas + 3) / 4, 256, lds))));
+    else if (ctx->sm.cross_kind == SC_IR_PARTNERS || ctx->sm.cross_kind == SC_IR_DENSE)
         HIPCHK(ctx, (launch_tu_scalar<L, (int)sizeof(VT), 1>(trace, make_launch(ctx, &q, (n_replicas + 3) / 4, 256, lds))));
     else
         HIPCHK(ctx, (launch_tu_scalar<L, (int)sizeof(VT), 0>(trace, make_launch(ctx, &q, (n_replicas + 3) / 4, 256, lds))));

@@ -50,7 +50,7 @@ hipError_t launch_tu_list_block(bool trace, const SearchLaunch& a);
 template <int L>
 hipError_t launch_tu_list_wave(bool trace, int mode, const SearchLaunch& a);
 // scalar engine: k_scalar_search_wave<L, TRACE, VT, IR>, VT = int8_t (VTB 1) or int16_t (VTB 2); IR = the unit built with the interpreted
-// pair-predicate joins (1) or without them (0: specialised joins only)
+// pair-predicate joins (1) or without them (0: specialised joins only), or the unit of the classes with several predicate joins (2)
 template <int L, int VTB, int IR>
 hipError_t launch_tu_scalar(bool trace, const SearchLaunch& a);
 // generic N-leaf engine: k_mixed_search_wave<L, TRACE, VT, RUIN, PREC, MODE> (mode 1 = the FAST instantiation of the default
@@ -78,7 +78,9 @@ SF_TU_DECL_MIXED(4, 2, true, true)
     template <>                                                                  \
     hipError_t launch_tu_scalar<L, VTB, 0>(bool trace, const SearchLaunch& a);   \
     template <>                                                                  \
-    hipError_t launch_tu_scalar<L, VTB, 1>(bool trace, const SearchLaunch& a);
+    hipError_t launch_tu_scalar<L, VTB, 1>(bool trace, const SearchLaunch& a);   \
+    template <>                                                                  \
+    hipError_t launch_tu_scalar<L, VTB, 2>(bool trace, const SearchLaunch& a);
 SF_TU_DECL_SCALAR(2, 1)
 SF_TU_DECL_SCALAR(2, 2)
 SF_TU_DECL_SCALAR(4, 1)

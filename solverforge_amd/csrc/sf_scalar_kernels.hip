@@ -45,6 +45,21 @@ struct PairTerm {
     const uint32_t* cval;
     const int64_t* table;
 };
+// A scalar class may carry up to SF_MAX_PAIR_JOINS predicate joins.  A class with ONE keeps it in ScalarModel's own join fields (cross_kind,
+// cross_level, ...), exactly as before; a class with two or more keeps ALL of them in a small device array of these records (ScalarModel::xj),
+// the own fields unused (cross_level -1).  Read with wave-uniform scalar loads, like the residual program `ir`.
+constexpr int SF_MAX_PAIR_JOINS = 4;
+struct PairJoin {
+    int32_t kind;              // ScalarCrossKind
+    int32_t level;
+    int64_t weight;
+    const uint32_t* pn_off;    // [n+1] symmetric partner CSR (SC_PARTNERS_EQUAL, SC_IR_PARTNERS)
+    const uint32_t* pn;
+    const int32_t* col;        // [n] column fact (SC_QUEENS)
+    const PairTerm* ir;        // [ir_n] residual program (SC_IR_*)
+    int32_t ir_n;
+    int32_t pad;
+};
 
 struct ScalarModel {
     int32_t n = 0;  // entities
@@ -62,6 +77,8 @@ struct ScalarModel {
     const int32_t* col = nullptr;      // [n] column fact (SC_QUEENS)
     int32_t ir_n = 0;                  // SC_IR_*: residual terms of the pair predicate, clause ids ascending
     const PairTerm* ir = nullptr;      // [ir_n] in device memory (wave-uniform reads: scalar loads on demand, nothing rides in the argument block)
+    const PairJoin* xj = nullptr;      // [n_xj] a class with two or more predicate joins: all of them, in declaration order (cross_level is then -1)
+    int32_t n_xj = 0;
     // value-keyed aggregates (per-value count / sum tables, maintained at apply):
     int32_t sj_level = -1, grp_level = -1;  // keyed self-join pairs; grouped sum
     int64_t sj_weight = 0, grp_weight = 0, grp_cap = -1;
@@ -133,12 +150,18 @@ __device__ __forceinline__ bool value_legal(const ScalarModel& m, uint32_t e, in
 // program is read with scalar loads, one term per trip of a loop that is NOT unrolled: inlined and unrolled at every pair of every
 // partner loop it tripled the build time of the search kernels), per-lane data; the column facts are read once for both values.
 // left = the lower entity index (the join's left.id < right.id).
-// SF_SCALAR_PAIR_IR (a scalar-engine unit is built twice, csrc/Makefile): 0 = the interpreted joins compile OUT of scalar_conflict_delta -- the unit of
+// SF_SCALAR_PAIR_IR (a scalar-engine unit is built three times, csrc/Makefile): 0 = the interpreted joins compile OUT of scalar_conflict_delta -- the unit of
 // the models whose program matched a specialised loop (graph colouring, queens, job-shop groups): their kernels do not carry the interpreter's live
 // ranges (with it in: 9 -> 61 spilled vector registers and -4 % on the default SA policy of graph colouring, profiles/r06k_pair_ir_ab.txt); 1 = the
 // unit the host launches for SC_IR_PARTNERS / SC_IR_DENSE models.  Every other unit (the generic engine, the C ABI) keeps both.  W = 4 everywhere (8 spills).
 #ifndef SF_SCALAR_PAIR_IR
 #define SF_SCALAR_PAIR_IR 1
+#endif
+// SF_SCALAR_MULTI_JOIN: 0 = the loop over the join records of a multi-join class (ScalarModel::xj) compiles out -- scalar units 0 / 1, launched for
+// the classes with at most one join, keep their code and register figures; 2 = ONLY that loop, the class's own join fields compile out -- scalar
+// unit 2, launched for the multi-join classes; 1 = both (every other unit: the generic engine, the C ABI).
+#ifndef SF_SCALAR_MULTI_JOIN
+#define SF_SCALAR_MULTI_JOIN 1
 #endif
 #ifndef SF_PAIR_IR_W
 #define SF_PAIR_IR_W 4  // partners of one entity evaluated side by side by the interpreted join (pair_program_holds2_w)
@@ -276,18 +299,20 @@ __device__ __forceinline__ void pair_program_holds2_w(const PairTerm* __restrict
 // returns conflicts(e, v_new) - conflicts(e, v_old) in ONE pass over the partner list, sixteen
 // partner ids in flight per iteration (the list lives in HBM/L2, the values in LDS): an average
 // graph-colouring row (degree 20) costs two memory round trips instead of twenty.
-// `vals` is anything indexable by entity: the replica's value array (const VT*) or a view of it (ValsView)
+// `vals` is anything indexable by entity: the replica's value array (const VT*) or a view of it (ValsView).
+// One join, given by its fields (the class's own join, or one PairJoin record of a multi-join class).
 template <class VA>
-__device__ __forceinline__ int64_t scalar_conflict_delta(const ScalarModel& m, const VA& vals, uint32_t e, int32_t v_new,
-                                                         int32_t v_old, uint32_t skip) {
+__device__ __forceinline__ int32_t join_conflict_delta(int32_t kind, const uint32_t* pn_off, const uint32_t* pn, const int32_t* col,
+                                                       const PairTerm* ir, int32_t ir_n, int32_t n,
+                                                       const VA& vals, uint32_t e, int32_t v_new, int32_t v_old, uint32_t skip) {
     int32_t c = 0;
-    if (m.cross_kind == SC_PARTNERS_EQUAL) {
-        const uint32_t p1 = m.pn_off[e + 1];
+    if (kind == SC_PARTNERS_EQUAL) {
+        const uint32_t p1 = pn_off[e + 1];
         constexpr int W = SF_CONFLICT_W;
-        for (uint32_t p = m.pn_off[e]; p < p1; p += W) {
+        for (uint32_t p = pn_off[e]; p < p1; p += W) {
             uint32_t o[W];
 #pragma unroll
-            for (int q = 0; q < W; ++q) o[q] = p + q < p1 ? m.pn[p + q] : skip;
+            for (int q = 0; q < W; ++q) o[q] = p + q < p1 ? pn[p + q] : skip;
 #pragma unroll
             for (int q = 0; q < W; ++q) {
                 if (o[q] == skip || p + q >= p1) continue;
@@ -297,47 +322,47 @@ __device__ __forceinline__ int64_t scalar_conflict_delta(const ScalarModel& m, c
             }
         }
 #if SF_SCALAR_PAIR_IR
-    } else if (m.cross_kind == SC_IR_PARTNERS) {  // the partner index names the pairs one clause admits, the program decides the rest
-        const uint32_t p1 = m.pn_off[e + 1];
+    } else if (kind == SC_IR_PARTNERS) {  // the partner index names the pairs one clause admits, the program decides the rest
+        const uint32_t p1 = pn_off[e + 1];
         constexpr int W = SF_PAIR_IR_W;
 #pragma unroll 1
-        for (uint32_t p = m.pn_off[e]; p < p1; p += W) {
+        for (uint32_t p = pn_off[e]; p < p1; p += W) {
             uint32_t o[W], h[W];
             bool on[W];
             int32_t vo[W];
 #pragma unroll
-            for (int q = 0; q < W; ++q) o[q] = p + q < p1 ? m.pn[p + q] : e;
+            for (int q = 0; q < W; ++q) o[q] = p + q < p1 ? pn[p + q] : e;
 #pragma unroll
             for (int q = 0; q < W; ++q) {
                 vo[q] = (int32_t)vals[o[q]];
                 on[q] = p + q < p1 && o[q] != skip && o[q] != e && vo[q] >= 0;
             }
-            pair_program_holds2_w<W>(m.ir, m.ir_n, e, o, on, v_new, v_old, vo, h);
+            pair_program_holds2_w<W>(ir, ir_n, e, o, on, v_new, v_old, vo, h);
 #pragma unroll
             for (int q = 0; q < W; ++q) c += (int32_t)(h[q] & 1u) - (int32_t)(h[q] >> 1);
         }
-    } else if (m.cross_kind == SC_IR_DENSE) {  // no clause to index by: every other assigned entity
+    } else if (kind == SC_IR_DENSE) {  // no clause to index by: every other assigned entity
         constexpr int W = SF_PAIR_IR_W;
 #pragma unroll 1
-        for (uint32_t b = 0; b < (uint32_t)m.n; b += W) {
+        for (uint32_t b = 0; b < (uint32_t)n; b += W) {
             uint32_t o[W], h[W];
             bool on[W];
             int32_t vo[W];
 #pragma unroll
             for (int q = 0; q < W; ++q) {
-                o[q] = b + q < (uint32_t)m.n ? b + q : e;
+                o[q] = b + q < (uint32_t)n ? b + q : e;
                 vo[q] = (int32_t)vals[o[q]];
-                on[q] = b + q < (uint32_t)m.n && o[q] != e && o[q] != skip && vo[q] >= 0;
+                on[q] = b + q < (uint32_t)n && o[q] != e && o[q] != skip && vo[q] >= 0;
             }
-            pair_program_holds2_w<W>(m.ir, m.ir_n, e, o, on, v_new, v_old, vo, h);
+            pair_program_holds2_w<W>(ir, ir_n, e, o, on, v_new, v_old, vo, h);
 #pragma unroll
             for (int q = 0; q < W; ++q) c += (int32_t)(h[q] & 1u) - (int32_t)(h[q] >> 1);
         }
 #endif
-    } else if (m.cross_kind == SC_QUEENS) {  // board.rs:30-44: distinct columns, same row or same diagonal
-        const int32_t ce = m.col[e];
-        for (uint32_t o = 0; o < (uint32_t)m.n; ++o) {
-            const int32_t vo = (int32_t)vals[o], co = m.col[o];
+    } else if (kind == SC_QUEENS) {  // board.rs:30-44: distinct columns, same row or same diagonal
+        const int32_t ce = col[e];
+        for (uint32_t o = 0; o < (uint32_t)n; ++o) {
+            const int32_t vo = (int32_t)vals[o], co = col[o];
             if (o == e || o == skip || vo < 0 || co == ce) continue;
             const int32_t dc = co > ce ? co - ce : ce - co;
             if (v_new >= 0) {
@@ -350,8 +375,30 @@ __device__ __forceinline__ int64_t scalar_conflict_delta(const ScalarModel& m, c
             }
         }
     }
-    return (int64_t)c;
+    return c;
 }
+template <class VA>
+__device__ __forceinline__ int64_t scalar_conflict_delta(const ScalarModel& m, const VA& vals, uint32_t e, int32_t v_new,
+                                                         int32_t v_old, uint32_t skip) {
+    return (int64_t)join_conflict_delta(m.cross_kind, m.pn_off, m.pn, m.col, m.ir, m.ir_n, m.n, vals, e, v_new, v_old, skip);
+}
+#if SF_SCALAR_MULTI_JOIN
+// The joins of a multi-join class: entity e's count delta of each one (v_new against v_old, the pair (e, skip) left out), weighted and summed per
+// score level into d.  Wave-uniform loop, the records read with scalar loads; each join runs the code of its kind.
+template <class VA>
+__device__ __forceinline__ void scalar_xj_delta(const ScalarModel& m, const VA& vals, uint32_t e, int32_t v_new, int32_t v_old, uint32_t skip,
+                                                int64_t (&d)[SF_MAX_LEVELS_CONST]) {
+#pragma unroll 1
+    for (int32_t t = 0; t < m.n_xj; ++t) {
+        const PairJoin& j = m.xj[t];
+        const int32_t c = join_conflict_delta(j.kind, j.pn_off, j.pn, j.col, j.ir, j.ir_n, m.n, vals, e, v_new, v_old, skip);
+        const int64_t w = (int64_t)((uint64_t)j.weight * (uint64_t)(int64_t)c);
+#pragma unroll
+        for (int k = 0; k < SF_MAX_LEVELS_CONST; ++k)
+            if (k == j.level) d[k] = wadd(d[k], w);
+    }
+}
+#endif
 
 // ---- consecutive-runs collector (stream/collector/runs.rs:11-229) over the per-(value, point) count table ----------------
 // The table sits behind the per-value count table (16-byte aligned): a pointer to the counts locates it.
@@ -444,6 +491,7 @@ struct ScalarDelta {
     bool doable;
     int64_t d_run = 0;  // change of the summed run excess (consecutive-runs collector)
     int64_t d_cost2 = 0;  // change of the second cost matrix's sum (ScalarModel::cost2)
+    int64_t d_xj[SF_MAX_LEVELS_CONST] = {0, 0, 0, 0};  // joins of a multi-join class: their weighted count changes, summed per score level
 };
 
 // grouped/scorer.rs:89-101: an empty group scores zero
@@ -526,8 +574,13 @@ __device__ __forceinline__ ScalarDelta eval_scalar_move_v(const ScalarModel& m, 
         if (value < 0 && !m.allows_unassigned) return r;
         r.doable = true;
         r.d_un = (int64_t)((value < 0 ? 1 : 0) - (old < 0 ? 1 : 0)) * (m.un_w ? (int64_t)m.un_w[a] : 1);
+#if SF_SCALAR_MULTI_JOIN != 2
         if (m.cross_level >= 0)
             r.d_cross = scalar_conflict_delta(m, vals, a, value, old, 0xFFFFFFFFu);
+#endif
+#if SF_SCALAR_MULTI_JOIN
+        scalar_xj_delta(m, vals, a, value, old, 0xFFFFFFFFu, r.d_xj);
+#endif
         if (m.sj_level >= 0) {  // joining a value of c members adds C(c, k-1) tuples; leaving one of c removes C(c-1, k-1)
             if (m.sj_arity == 2)
                 r.d_pairs = (value >= 0 ? (int64_t)cnt[value] : 0) - (old >= 0 ? (int64_t)cnt[old] - 1 : 0);
@@ -591,8 +644,14 @@ __device__ __forceinline__ ScalarDelta eval_scalar_move_v(const ScalarModel& m, 
         r.doable = true;
         if (m.un_w)  // the None moves to the other entity: the count stays, the per-entity weights differ
             r.d_un = (int64_t)((vb < 0 ? 1 : 0) - (va < 0 ? 1 : 0)) * ((int64_t)m.un_w[a] - (int64_t)m.un_w[b]);
+#if SF_SCALAR_MULTI_JOIN != 2
         if (m.cross_level >= 0)
             r.d_cross = scalar_conflict_delta(m, vals, a, vb, va, b) + scalar_conflict_delta(m, vals, b, va, vb, a);
+#endif
+#if SF_SCALAR_MULTI_JOIN  // the pair (a, b) itself is skipped by both halves: every value op is symmetric in the two values, a swap keeps its status
+        scalar_xj_delta(m, vals, a, vb, va, b, r.d_xj);
+        scalar_xj_delta(m, vals, b, va, vb, a, r.d_xj);
+#endif
         if (m.cost_level >= 0) {
             const size_t ra = (size_t)a * m.n_values, rb = (size_t)b * m.n_values;
             const int64_t after = wadd(vb >= 0 ? m.cost[ra + vb] : 0, va >= 0 ? m.cost[rb + va] : 0);
@@ -739,6 +798,9 @@ __device__ __forceinline__ ScoreV<L> apply_scalar_delta(const ScalarModel& m, co
         if (k == m.cost2_level) s.v[k] = wsub(s.v[k], d.d_cost2);
         if (k == m.ex_level) s.v[k] = wsub(s.v[k], (int64_t)((uint64_t)m.ex_weight * (uint64_t)d.d_ex));
         if (k == m.run_level) s.v[k] = wsub(s.v[k], (int64_t)((uint64_t)m.run_weight * (uint64_t)d.d_run));
+#if SF_SCALAR_MULTI_JOIN
+        s.v[k] = wsub(s.v[k], d.d_xj[k]);
+#endif
     }
     return s;
 }
@@ -1087,6 +1149,35 @@ __global__ __launch_bounds__(64) void k_scalar_step_decide(ScalarModel m, Search
     }
 }
 
+// full evaluation of one join: the pairs (e, o > e) that match, e assigned with value v -- every matched pair is counted at its lower index
+__device__ __forceinline__ uint32_t join_matches_above(int32_t kind, const uint32_t* pn_off, const uint32_t* pn, const int32_t* col, const PairTerm* ir,
+                                                       int32_t ir_n, int32_t n, const int32_t* vals, uint32_t e, int32_t v) {
+    uint32_t cross = 0;
+    if (kind == SC_PARTNERS_EQUAL) {
+        for (uint32_t p = pn_off[e]; p < pn_off[e + 1]; ++p) {
+            const uint32_t o = pn[p];
+            if (o > e && vals[o] == v) ++cross;
+        }
+    } else if (kind == SC_IR_PARTNERS) {
+        for (uint32_t p = pn_off[e]; p < pn_off[e + 1]; ++p) {
+            const uint32_t o = pn[p];
+            if (o > e && vals[o] >= 0 && (pair_program_holds2(ir, ir_n, e, o, v, -1, vals[o]) & 1u)) ++cross;
+        }
+    } else if (kind == SC_IR_DENSE) {
+        for (uint32_t o = e + 1; o < (uint32_t)n; ++o)
+            if (vals[o] >= 0 && (pair_program_holds2(ir, ir_n, e, o, v, -1, vals[o]) & 1u)) ++cross;
+    } else if (kind == SC_QUEENS) {
+        const int32_t ce = col[e];
+        for (uint32_t o = e + 1; o < (uint32_t)n; ++o) {
+            const int32_t vo = vals[o], co = col[o];
+            if (vo < 0 || co == ce) continue;
+            const int32_t dr = vo > v ? vo - v : v - vo, dc = co > ce ? co - ce : ce - co;
+            if (vo == v || dr == dc) ++cross;
+        }
+    }
+    return cross;
+}
+
 // evaluate_all / initialize: full recomputation (fresh_score; FullAssert).  grid = R blocks.
 // accumulate != 0: add this class's constraint scores to what the list class already wrote (mixed models)
 SF_PLAIN_KERNEL
@@ -1094,6 +1185,7 @@ __global__ __launch_bounds__(256) void k_scalar_evaluate_all(ScalarModel m, int6
                                                              int accumulate, int64_t* out_parts = nullptr) {
     extern __shared__ __attribute__((aligned(16))) unsigned char tab_mem[];  // per-value tables (when used)
     __shared__ unsigned long long s_un, s_cross, s_pairs, s_grp, s_groups, s_cost, s_cost_n, s_ex, s_ex_n, s_run, s_run_groups, s_un_n, s_cost2;
+    __shared__ unsigned long long s_xj[SF_MAX_PAIR_JOINS];  // matches of each join of a multi-join class
     const int r = blockIdx.x;
     const int32_t* vals = m.vals + (size_t)r * m.n;
     const bool tables = m.tables();
@@ -1109,6 +1201,7 @@ __global__ __launch_bounds__(256) void k_scalar_evaluate_all(ScalarModel m, int6
         s_cost2 = 0;
         s_run = s_run_groups = 0;
         s_un_n = 0;
+        for (int t = 0; t < SF_MAX_PAIR_JOINS; ++t) s_xj[t] = 0;
     }
     if (tables)
         for (int v = threadIdx.x; v < m.n_values; v += blockDim.x) {
@@ -1162,7 +1255,7 @@ __global__ __launch_bounds__(256) void k_scalar_evaluate_all(ScalarModel m, int6
             }
         }
     }
-    unsigned long long un = 0, un_n = 0, cross = 0, cost = 0, cost_n = 0, cost2 = 0;
+    unsigned long long un = 0, un_n = 0, cross = 0, cost = 0, cost_n = 0, cost2 = 0, xj[SF_MAX_PAIR_JOINS] = {0, 0, 0, 0};
     for (uint32_t e = threadIdx.x; e < (uint32_t)m.n; e += blockDim.x) {
         const int32_t v = vals[e];
         if (v < 0) {
@@ -1175,31 +1268,13 @@ __global__ __launch_bounds__(256) void k_scalar_evaluate_all(ScalarModel m, int6
             cost_n += c != 0 ? 1 : 0;
         }
         if (m.cost2_level >= 0 && v >= 0) cost2 += (unsigned long long)m.cost2[(size_t)e * m.n_values + v];
-        if (m.cross_level >= 0 && v >= 0) {
-            // every matched pair is seen from both sides: count it at its lower index
-            if (m.cross_kind == SC_PARTNERS_EQUAL) {
-                for (uint32_t p = m.pn_off[e]; p < m.pn_off[e + 1]; ++p) {
-                    const uint32_t o = m.pn[p];
-                    if (o > e && vals[o] == v) ++cross;
-                }
-            } else if (m.cross_kind == SC_IR_PARTNERS) {
-                for (uint32_t p = m.pn_off[e]; p < m.pn_off[e + 1]; ++p) {
-                    const uint32_t o = m.pn[p];
-                    if (o > e && vals[o] >= 0 && (pair_program_holds2(m.ir, m.ir_n, e, o, v, -1, vals[o]) & 1u)) ++cross;
-                }
-            } else if (m.cross_kind == SC_IR_DENSE) {
-                for (uint32_t o = e + 1; o < (uint32_t)m.n; ++o)
-                    if (vals[o] >= 0 && (pair_program_holds2(m.ir, m.ir_n, e, o, v, -1, vals[o]) & 1u)) ++cross;
-            } else if (m.cross_kind == SC_QUEENS) {
-                const int32_t ce = m.col[e];
-                for (uint32_t o = e + 1; o < (uint32_t)m.n; ++o) {
-                    const int32_t vo = vals[o], co = m.col[o];
-                    if (vo < 0 || co == ce) continue;
-                    const int32_t dr = vo > v ? vo - v : v - vo, dc = co > ce ? co - ce : ce - co;
-                    if (vo == v || dr == dc) ++cross;
-                }
+        if (m.cross_level >= 0 && v >= 0) cross += join_matches_above(m.cross_kind, m.pn_off, m.pn, m.col, m.ir, m.ir_n, m.n, vals, e, v);
+#pragma unroll
+        for (int t = 0; t < SF_MAX_PAIR_JOINS; ++t)
+            if (t < m.n_xj && v >= 0) {
+                const PairJoin& j = m.xj[t];
+                xj[t] += join_matches_above(j.kind, j.pn_off, j.pn, j.col, j.ir, j.ir_n, m.n, vals, e, v);
             }
-        }
     }
     atomicAdd(&s_un, un);
     atomicAdd(&s_un_n, un_n);
@@ -1207,6 +1282,9 @@ __global__ __launch_bounds__(256) void k_scalar_evaluate_all(ScalarModel m, int6
     atomicAdd(&s_cost, cost);
     atomicAdd(&s_cost_n, cost_n);
     atomicAdd(&s_cost2, cost2);
+#pragma unroll
+    for (int t = 0; t < SF_MAX_PAIR_JOINS; ++t)
+        if (t < m.n_xj) atomicAdd(&s_xj[t], xj[t]);
     __syncthreads();
     if (threadIdx.x == 0) {
         int64_t sc[SF_MAX_LEVELS_CONST] = {0, 0, 0, 0};
@@ -1218,6 +1296,7 @@ __global__ __launch_bounds__(256) void k_scalar_evaluate_all(ScalarModel m, int6
         if (m.cost2_level >= 0) sc[m.cost2_level] = wsub(sc[m.cost2_level], (int64_t)s_cost2);
         if (m.ex_level >= 0) sc[m.ex_level] = wsub(sc[m.ex_level], (int64_t)((uint64_t)m.ex_weight * s_ex));
         if (m.run_level >= 0) sc[m.run_level] = wsub(sc[m.run_level], (int64_t)((uint64_t)m.run_weight * s_run));
+        for (int32_t t = 0; t < m.n_xj; ++t) sc[m.xj[t].level] = wsub(sc[m.xj[t].level], (int64_t)((uint64_t)m.xj[t].weight * s_xj[t]));
         for (int k = 0; k < m.levels; ++k) {
             if (out_scores) out_scores[(size_t)r * m.levels + k] = accumulate ? wadd(out_scores[(size_t)r * m.levels + k], sc[k]) : sc[k];
             if (commit) m.score[(size_t)r * 4 + k] = accumulate ? wadd(m.score[(size_t)r * 4 + k], sc[k]) : sc[k];
@@ -1236,6 +1315,7 @@ __global__ __launch_bounds__(256) void k_scalar_evaluate_all(ScalarModel m, int6
             q[14] = (int64_t)s_run;
             q[15] = (int64_t)s_run_groups;
             q[16] = (int64_t)s_un_n;
+            for (int32_t t = 0; t < m.n_xj; ++t) q[SF_EACH_XJ + t] = (int64_t)s_xj[t];
         }
     }
 }
@@ -1362,8 +1442,9 @@ struct SCarve {
 };
 
 // VT = int8_t (n_values <= 127) or int16_t: the replica's values in LDS
-// IRK = SF_SCALAR_PAIR_IR of the unit that instantiates it: the two builds of one (L, TRACE, VT) are different kernels by name
-template <int L, bool TRACE, class VT, bool IRK = (SF_SCALAR_PAIR_IR != 0)>
+// IRK = the scalar unit that instantiates it (0 / 1 = SF_SCALAR_PAIR_IR, 2 = the multi-join unit): the three builds of one (L, TRACE, VT) are
+// different kernels by name
+template <int L, bool TRACE, class VT, int IRK = (SF_SCALAR_MULTI_JOIN == 2 ? 2 : (SF_SCALAR_PAIR_IR != 0 ? 1 : 0))>
 #ifndef SF_SCALAR_BLOCKS_PER_CU
 #define SF_SCALAR_BLOCKS_PER_CU 3  // (round 5: 168 registers, 26-33 spilled values; 12 replicas per CU -- graph colouring 10k: LateAcceptance 6.85 -> 8.45 G moves/s, the default SimulatedAnnealing policy 82 -> 103 M, profiles/r05_graph_occupancy.txt)
 #endif

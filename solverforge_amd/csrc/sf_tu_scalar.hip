@@ -1,10 +1,12 @@
-// One translation unit of the scalar engine: k_scalar_search_wave<SF_TU_L, *, VT>, traced and untraced -- built twice per (L, VT): SF_TU_IR = 0 without
-// the interpreted pair-predicate joins (the models whose program matched a specialised loop), 1 with them (four partners side by side; eight spill:
-// graph colouring interpreted 5.9 -> 4.8 G moves/s, profiles/r06k_pair_ir_ab.txt).
+// One translation unit of the scalar engine: k_scalar_search_wave<SF_TU_L, *, VT>, traced and untraced -- built three times per (L, VT): SF_TU_IR = 0
+// without the interpreted pair-predicate joins (the models whose program matched a specialised loop), 1 with them (four partners side by side; eight
+// spill: graph colouring interpreted 5.9 -> 4.8 G moves/s, profiles/r06k_pair_ir_ab.txt), 2 = the classes with several predicate joins: the loop over
+// their join records, each join specialised or interpreted (units 0 and 1 do not carry that loop).
 #ifndef SF_TU_IR
 #define SF_TU_IR 1
 #endif
-#define SF_SCALAR_PAIR_IR SF_TU_IR
+#define SF_SCALAR_PAIR_IR (SF_TU_IR != 0)
+#define SF_SCALAR_MULTI_JOIN (SF_TU_IR == 2 ? 2 : 0)
 #if !SF_TU_IR && !defined(SF_CONFLICT_W)
 #define SF_CONFLICT_W 8  // partner ids in flight per pass of the specialised join: 8 / 16 / 24 / 32 -> 10.0 / 9.8 / 9.3 / 9.4 G on graph colouring (profiles/r06k_pair_ir_ab.txt)
 #endif

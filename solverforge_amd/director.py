@@ -194,7 +194,9 @@ class GpuScoreDirector:
 
     def add_pair_join(self, descriptor_index, terms, level=0, weight=1, variable_index=0):
         """Predicate join of a scalar class with itself, the predicate as data (sf_constraint_add_pair_join): `terms` = sequence of
-        (op, clause, fact, fact_b, param) -- a conjunction of clauses, each a disjunction of its terms (PairOp names the ops)."""
+        (op, clause, fact, fact_b, param) -- a conjunction of clauses, each a disjunction of its terms (PairOp names the ops).  May be called
+        up to four times per class (the CROSS_* preset constraints count too), each join with its own level and weight; evaluate_each gives
+        one row per join."""
         arr = np.zeros(len(terms), dtype=np.dtype([("op", np.int32), ("clause", np.int32), ("fact", np.int32), ("fact_b", np.int32), ("param", np.int64)]))
         for i, t in enumerate(terms):
             t = tuple(t) + (-1, -1, 0)[len(t) - 2:] if len(t) < 5 else tuple(t)
