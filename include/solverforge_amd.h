@@ -691,6 +691,25 @@ int32_t sf_solver_get_engine(sf_ctx* ctx, int32_t* out_engine); /* the engine la
  * neighbour index renumbered along a nearest-neighbour chain once they outgrow the L2: DESIGN 11.3; SF_AMD_RENUMBER=0 / 1 overrides).
  * The numbering is invisible at this boundary: every id that crosses it is the caller's. */
 int32_t sf_list_wave_layout(sf_ctx* ctx, int32_t* out_mode, int32_t* out_renumbered);
+/* Which narrow-arithmetic paths the list model qualified for and the last generic-engine launch took (diagnostics; tests assert the
+ * side of each host range check they mean to cover).  Reads state recorded at sf_initialize / launch; changes nothing.
+ * out_model = sf_arith_model_bits of the list model (0 without one) and the scalar engine's value bytes;
+ * out_last_generic = sf_generic_launch_bits of the last generic-engine launch, -1 = none yet. */
+typedef enum sf_arith_model_bits {
+    SF_ARITH_MAT32 = 1,    /* u32 copy of the distance matrix: every finite leg < 0xFFFFFFFF */
+    SF_ARITH_MAT16 = 2,    /* u16 copy: every finite leg < 0xFFFF */
+    SF_ARITH_LEG16 = 4,    /* 16-bit ruin leg tables: symmetric, u32 copy, every finite leg < 0xFFFF, dim <= 65535 */
+    SF_ARITH_SMALL32 = 8,  /* 32-bit trial deltas: every leg finite and the weight / demand / capacity bounds of sf_initialize */
+    SF_ARITH_SCALAR_VT_SHIFT = 8  /* bits 8-11: bytes of the value type of the last scalar-engine launch (0 = none yet) */
+} sf_arith_model_bits;
+typedef enum sf_generic_launch_bits {
+    SF_GEN_FAST = 1,         /* the FAST instantiation (the default list policy on a list-only model) */
+    SF_GEN_NODE_GLOBAL = 2,  /* the node -> slot table in HBM */
+    SF_GEN_RING32 = 4,       /* the 32-bit pre-evaluated delta ring */
+    SF_GEN_RUIN_SHIFT = 4,   /* bits 4-5: ruin recreate, 0 none / 1 general (matrix gathers) / 2 16-bit leg tables / 3 list-preserving (v2) */
+    SF_GEN_VT_SHIFT = 8      /* bits 8-11: bytes of the scalar value type */
+} sf_generic_launch_bits;
+int32_t sf_list_arith_flags(sf_ctx* ctx, int32_t* out_model, int32_t* out_last_generic);
 /* explicit step seeds for parity runs (n_steps per replica, replica-major); NULL clears */
 int32_t sf_solver_set_step_seeds(sf_ctx* ctx, const uint64_t* seeds, int64_t n_steps);
 /* ≙ phase start: last_step_score = calculate_score, acceptor.phase_started, best = working.  Zeroes the replicas' counters (sf_get_stats

@@ -74,6 +74,7 @@ def lib():
             "sfo_balance_create_nary": (vp, [i32, i32, vp, vp, i64, i64, i32]),
             "sfo_balance_create_base": (vp, [i32, i32, vp, vp, i64, i64]),
             "sfo_cvrp_create": (vp, [i32, i32, i64, i32, i32, vp, vp, vp, vp, vp]),
+            "sfo_cvrp_create_weighted": (vp, [i32, i32, i64, i32, i32, vp, vp, vp, vp, vp, i64, i64, i64]),
             "sfo_assignment_create": (vp, [i32, i32, vp, vp, i64, vp, i32, i32, i64]),
             "sfo_assignment_create2": (vp, [i32, i32, vp, vp, i64, vp, i32, i32, i64, vp, i32]),
             "sfo_list_toy_create": (vp, [i32, vp, vp, i32]),
@@ -209,15 +210,17 @@ class Model:
         return Model(h, [len(values)])
 
     @staticmethod
-    def cvrp(capacity, depot, demands, matrix, customers, routes):
+    def cvrp(capacity, depot, demands, matrix, customers, routes, weights=(1, 1, 1)):
+        """weights = (all_customers_assigned, vehicle_capacity, total_distance) constraint weights."""
         demands = np.ascontiguousarray(demands, dtype=np.int32)
         matrix = np.ascontiguousarray(matrix, dtype=np.int64)
         customers = np.ascontiguousarray(customers, dtype=np.uint32)
         off, vals = csr(routes)
         dim = matrix.shape[0]
-        h = lib().sfo_cvrp_create(
+        wa, wc, wd = (int(w) for w in weights)
+        h = lib().sfo_cvrp_create_weighted(
             len(customers), len(routes), int(capacity), int(depot), dim, _p(demands), _p(matrix), _p(customers),
-            _p(off), _p(vals),
+            _p(off), _p(vals), wa, wc, wd,
         )
         return Model(h, [len(routes)])
 

@@ -172,6 +172,14 @@ void* sfo_cvrp_create(int32_t n_customers, int32_t n_vehicles, int64_t capacity,
                      matrix, customers, route_off, route_vals)
         .release();
 }
+void* sfo_cvrp_create_weighted(int32_t n_customers, int32_t n_vehicles, int64_t capacity, int32_t depot, int32_t dim,
+                               const int32_t* demands, const int64_t* matrix, const uint32_t* customers,
+                               const uint32_t* route_off, const uint32_t* route_vals, int64_t w_assigned, int64_t w_cap,
+                               int64_t w_dist) {
+    return make_cvrp((size_t)n_customers, (size_t)n_vehicles, capacity, (size_t)depot, (size_t)dim, demands,
+                     matrix, customers, route_off, route_vals, w_assigned, w_cap, w_dist)
+        .release();
+}
 void* sfo_precedence_shop_create(int32_t n_nodes, int32_t n_owners, const int64_t* duration, const uint32_t* succ_off, const uint32_t* succ,
                                  const int64_t* expected_owner, const uint32_t* list_off, const uint32_t* list_vals, int32_t levels,
                                  int32_t hard_levels, int32_t hard_level, int32_t soft_level) {

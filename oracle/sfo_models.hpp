@@ -553,7 +553,9 @@ inline int64_t cvrp_route_load(const CvrpFacts& f, const std::vector<uint32_t>& 
 inline std::unique_ptr<Model> make_cvrp(size_t n_customers, size_t n_vehicles, int64_t capacity, size_t depot,
                                         size_t dim, const int32_t* demands, const int64_t* matrix,
                                         const uint32_t* customers, const uint32_t* route_off,
-                                        const uint32_t* route_vals) {
+                                        const uint32_t* route_vals, int64_t w_assigned = 1, int64_t w_cap = 1,
+                                        int64_t w_dist = 1) {
+    // w_*: the constraint weights (the reference's penalize(HardSoftScore::of_hard(w)) / of_soft(w)); the model's own are all 1
     auto m = std::make_unique<Model>();
     auto facts = std::make_shared<CvrpFacts>();
     facts->capacity = capacity;
@@ -585,7 +587,7 @@ inline std::unique_ptr<Model> make_cvrp(size_t n_customers, size_t n_vehicles, i
     assigned->flatten = [](const Solution& s, size_t p, std::vector<int64_t>& out) {
         for (uint32_t v : s.classes[0].lists[p]) out.push_back((int64_t)v);
     };
-    assigned->weight = [](const Solution&, size_t) { return Score::of(1, 0); };
+    assigned->weight = [w_assigned](const Solution&, size_t) { return Score::of(w_assigned, 0); };
     assigned->indexed_usize = true;
     m->director.constraints.members.push_back(std::move(assigned));
 
@@ -595,9 +597,9 @@ inline std::unique_ptr<Model> make_cvrp(size_t n_customers, size_t n_vehicles, i
     cap->source = ChangeSource::descriptor(0);
     cap->count = [](const Solution& s) { return s.classes[0].n; };
     cap->filter = [](const Solution&, size_t) { return true; };
-    cap->weight = [cf](const Solution& s, size_t r) {
+    cap->weight = [cf, w_cap](const Solution& s, size_t r) {
         int64_t over = wrap_sub(cvrp_route_load(*cf, s.classes[0].lists[r]), cf->capacity);
-        return Score::of(over > 0 ? over : 0, 0);
+        return Score::of(wrap_mul(w_cap, over > 0 ? over : 0), 0);
     };
     m->director.constraints.members.push_back(std::move(cap));
 
@@ -607,8 +609,8 @@ inline std::unique_ptr<Model> make_cvrp(size_t n_customers, size_t n_vehicles, i
     dist->source = ChangeSource::descriptor(0);
     dist->count = [](const Solution& s) { return s.classes[0].n; };
     dist->filter = [](const Solution&, size_t) { return true; };
-    dist->weight = [cf](const Solution& s, size_t r) {
-        return Score::of(0, cvrp_route_distance(*cf, s.classes[0].lists[r]));
+    dist->weight = [cf, w_dist](const Solution& s, size_t r) {
+        return Score::of(0, wrap_mul(w_dist, cvrp_route_distance(*cf, s.classes[0].lists[r])));
     };
     m->director.constraints.members.push_back(std::move(dist));
 

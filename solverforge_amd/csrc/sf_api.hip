@@ -108,6 +108,8 @@ struct sf_ctx {
     NbrIndex nbr_wave{nullptr};   // ... and its neighbour index
     bool wave_renumbered = false;
     int last_wave_mode = -1;      // launch mode of the last wave-engine launch (sf_list_wave_layout)
+    int32_t last_generic_flags = -1;  // what the last generic-engine launch took (sf_list_arith_flags)
+    int32_t last_scalar_value_bytes = 0;  // value-type bytes of the last scalar-engine launch (sf_list_arith_flags)
     int xown_level = -1;             // SF_C_CROSS_OWNER_MATCH of a mixed model: level / weight / the [R][n_scalar] entity -> holding list map
     int64_t xown_weight = 0;
     std::vector<UniComponent> uni_components;  // non-empty: ScalarModel::cost is the fold of these (uni programs + at most one SF_C_VALUE_COST)
@@ -2543,6 +2545,18 @@ int32_t sf_list_wave_layout(sf_ctx* ctx, int32_t* out_mode, int32_t* out_renumbe
     return SF_OK;
 }
 
+int32_t sf_list_arith_flags(sf_ctx* ctx, int32_t* out_model, int32_t* out_last_generic) {
+    if (!ctx || !out_model || !out_last_generic) return fail(ctx, SF_ERR_INVALID, "sf_list_arith_flags: null argument");
+    if (!ctx->initialized) return fail(ctx, SF_ERR_INVALID, "sf_initialize first");
+    const ListModel& lm = ctx->lm;
+    *out_model = !ctx->has_list_model ? 0
+                                      : (lm.mat32 ? SF_ARITH_MAT32 : 0) | (lm.mat16 ? SF_ARITH_MAT16 : 0) | (lm.leg16 ? SF_ARITH_LEG16 : 0) |
+                                            (lm.small32 ? SF_ARITH_SMALL32 : 0);
+    *out_model |= ctx->last_scalar_value_bytes << SF_ARITH_SCALAR_VT_SHIFT;
+    *out_last_generic = ctx->last_generic_flags;
+    return SF_OK;
+}
+
 int32_t sf_solver_set_step_seeds(sf_ctx* ctx, const uint64_t* seeds, int64_t n_steps) {
     DeviceGuard _dev(ctx);
     if (!ctx) return SF_ERR_INVALID;
@@ -2668,6 +2682,13 @@ static int launch_mixed_t(sf_ctx* ctx, const SearchParams& p, const GLeaves& gl,
             std::fprintf(stderr, "[sf] generic engine launch: L=%d ruin=%d prec=%d fast=%d prec_occ=%d replicas=%d LDS/replica=%zu B (prec groups %d, static %d B) waves/workgroup=%d resident/CU=%zu\n",
                          L, (int)RUIN, (int)PREC, (int)fast, (int)prec_occ, n_replicas, cv.total, PREC ? gl.prec_groups : 0, PREC ? gl.prec_static : 0, wpb, best_resident);
         }
+    }
+    {  // recorded for sf_list_arith_flags only; the kernels' own choice of ruin recreate is the same (sf_mixed_wave.hip: `v2`)
+        const ListModel& lm = ctx->lm;
+        const bool v2_ok = lm.V <= 128 && lm.n_cap <= 32767 && lm.dim <= 32767 && lm.small32 && lm.mat16;  // rv2_model_ok
+        const int ruin_variant = !gl.has_ruin ? 0 : fast ? 3 : !lm.leg16 ? 1 : v2_ok ? 3 : 2;
+        ctx->last_generic_flags = (fast ? SF_GEN_FAST : 0) | (nodeg ? SF_GEN_NODE_GLOBAL : 0) | (gl2.ringd ? SF_GEN_RING32 : 0) |
+                                  (ruin_variant << SF_GEN_RUIN_SHIFT) | ((int32_t)sizeof(VT) << SF_GEN_VT_SHIFT);
     }
     SearchParams q = p;
     q.n_launch = n_replicas;

@@ -499,6 +499,7 @@ static int launch_scalar_search(sf_ctx* ctx, SearchParams& p, int grid, bool tra
             }
     if (p.n_leaves == 0) return fail(ctx, SF_ERR_INVALID, "no scalar selector configured");
     const bool small = ctx->sm.n_values <= 127;
+    ctx->last_scalar_value_bytes = small ? 1 : 2;  // (sf_list_arith_flags)
 #define SF_SCALAR_CASE(LV)                                                                                     \
     case LV:                                                                                                   \
         if (small)                                                                                             \

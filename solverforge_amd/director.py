@@ -574,6 +574,20 @@ class GpuScoreDirector:
         check(self._L.sf_list_wave_layout(self._h, C.byref(m), C.byref(n)), self._h)
         return m.value, bool(n.value)
 
+    def arith_flags(self):
+        """Narrow-arithmetic paths (sf_list_arith_flags): the list model's {"mat32", "mat16", "leg16", "small32",
+        "scalar_value_bytes" (of the last scalar-engine launch, 0 = none)} and what the last generic-engine launch took --
+        {"fast", "node_global", "ring32", "ruin" (0 none / 1 general / 2 leg16 / 3 v2), "value_bytes"}, or None before the
+        first one.  Diagnostics for tests."""
+        m, g = C.c_int32(0), C.c_int32(0)
+        check(self._L.sf_list_arith_flags(self._h, C.byref(m), C.byref(g)), self._h)
+        model = {"mat32": bool(m.value & 1), "mat16": bool(m.value & 2), "leg16": bool(m.value & 4), "small32": bool(m.value & 8),
+                 "scalar_value_bytes": (m.value >> 8) & 15}
+        g = g.value
+        gen = None if g < 0 else {"fast": bool(g & 1), "node_global": bool(g & 2), "ring32": bool(g & 4), "ruin": (g >> 4) & 3,
+                                  "value_bytes": (g >> 8) & 15}
+        return model, gen
+
     def best_scores(self):
         return self._scores(self._L.sf_get_best_scores)
 

@@ -9,13 +9,14 @@ FACT_MATRIX, FACT_DEMAND, FACT_CUSTOMERS, FACT_ADJ, FACT_GROUP, FACT_COLUMN, FAC
 
 
 def build_cvrp(problem, n_replicas=1, device_id=0, max_nearby=20, leaves=("nearby_change", "nearby_swap"),
-               sublist_sizes=(1, 3), kopt=(1, 20), ruin=(2, 5, 10), permute=(2, 5)):
+               sublist_sizes=(1, 3), kopt=(1, 20), ruin=(2, 5, 10), permute=(2, 5), weights=(1, 1, 1)):
     # leaves may also name the plain streams "list_change" / "list_swap" (generic N-leaf engine)
     """CVRP: HardSoftScore; all_customers_assigned (not-exists, 1 hard each —
     crates/solverforge/tests/list_clarke_wright_publication/domain/publication_plan.rs:51-65),
     vehicle_capacity (uni on routes, max(0, load-cap) hard), total_distance (uni on routes,
     depot->...->depot, soft); leaves = default list policy nearby change + nearby swap with
-    MatrixDistanceMeter, max_nearby 20 (default_local_search/policy/list.rs:19,97-141)."""
+    MatrixDistanceMeter, max_nearby 20 (default_local_search/policy/list.rs:19,97-141).
+    weights = the three constraints' weights in that order (the model's own are 1, 1, 1)."""
     d = GpuScoreDirector(score_levels=2, hard_levels=1, n_replicas=n_replicas, device_id=device_id)
     n_vehicles = len(problem["routes"])
     dim = problem["matrix"].shape[0]
@@ -24,9 +25,10 @@ def build_cvrp(problem, n_replicas=1, device_id=0, max_nearby=20, leaves=("nearb
     d.add_fact_matrix(FACT_MATRIX, problem["matrix"])
     d.add_fact_column_i32(FACT_DEMAND, problem["demands"])
     d.add_fact_column_u32(FACT_CUSTOMERS, problem["customers"])
-    d.add_constraint(ConstraintKind.NOT_EXISTS_FLATTENED, 0, fact=FACT_CUSTOMERS, level=0, weight=1)
-    d.add_constraint(ConstraintKind.ROUTE_CAPACITY, 0, fact=FACT_DEMAND, param=int(problem["capacity"]), level=0, weight=1)
-    d.add_constraint(ConstraintKind.ROUTE_DISTANCE, 0, fact=FACT_MATRIX, param=int(problem["depot"]), level=1, weight=1)
+    w_assigned, w_cap, w_dist = (int(w) for w in weights)
+    d.add_constraint(ConstraintKind.NOT_EXISTS_FLATTENED, 0, fact=FACT_CUSTOMERS, level=0, weight=w_assigned)
+    d.add_constraint(ConstraintKind.ROUTE_CAPACITY, 0, fact=FACT_DEMAND, param=int(problem["capacity"]), level=0, weight=w_cap)
+    d.add_constraint(ConstraintKind.ROUTE_DISTANCE, 0, fact=FACT_MATRIX, param=int(problem["depot"]), level=1, weight=w_dist)
     # selectors are declared in the order `leaves` names them: a configured root union (configure_union) schedules and weights
     # its children in declaration order; the default policy's union ignores it (policy/list.rs:24-33 order)
     for leaf in leaves:
