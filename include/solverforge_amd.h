@@ -607,12 +607,41 @@ int32_t sf_construct_list_regret(sf_ctx* ctx, int32_t descriptor_index, const ui
  * route-local 2-opt polishing the default construction runs after Clarke-Wright, with the stock CVRP route hooks (the model's
  * depot, distance_cost legs of the attached matrix).  k: only 2 is implemented by the reference, every other value is a scored
  * no-op.  feasible_mode 0 = no feasibility hook, 1 = the capacity test of route_hooks::feasible (an over-capacity route takes no
- * reversal).  Every route with >= 4 visits of every replica is swept to its 2-opt local optimum in the reference's candidate
+ * reversal), 2 = the complete route_hooks::feasible (helpers.rs:109-119): capacity + the time windows of sf_list_set_time_windows; an
+ * improving reversal is judged on the whole reversed route as it stands then, and one that arrives after a window has closed is
+ * not taken and counts as a candidate only.  Mode 2 without windows or without the demand column is SF_ERR_INVALID, as is every other
+ * mode value.  Every route with >= 4 visits of every replica is swept to its 2-opt local optimum in the reference's candidate
  * order (first improving reversal applied in place); max_sweeps >= 1 bounds the sweeps per route (the phase's termination policy:
  * on an asymmetric metric the 2-opt delta ignores the reversed inner legs and need not converge).  Counters: one generated + evaluated candidate per (i, j), one accepted move
  * per reversal, applied = the accepted reversals of a changed route, one step + score calculation per changed route.  Commits the
  * score of the resulting lists; out_scores[n_replicas * score_levels] may be NULL. */
 int32_t sf_construct_list_k_opt(sf_ctx* ctx, int32_t descriptor_index, int32_t k, int32_t feasible_mode, int32_t max_sweeps, int64_t* out_scores);
+
+/* ≙ ProblemData{time_windows, service_durations, travel_times, vehicle_departure_time} (crates/solverforge-cvrp/src/problem_data.rs:20-23)
+ * of the list class's route owner: lo / hi / service[n_nodes], travel[n_nodes * n_nodes] row-major, in the caller's node ids.  Valid once
+ * the list variable is declared, before or after sf_initialize; a second call replaces the first.  n_nodes must equal the list
+ * variable's element id bound (the matrix dimension when a distance matrix is attached); a NULL array is SF_ERR_INVALID.  Before
+ * sf_initialize the final bound is not known yet: any n_nodes >= the declared element id bound is taken and copied, and a value that
+ * turns out wrong makes sf_initialize itself return SF_ERR_INVALID.  Values are
+ * not range-checked: a negative service duration, lo > hi, a negative or UNREACHABLE (INT64_MAX) travel entry are data that make
+ * routes infeasible, exactly as in helpers.rs:181-218.  Read by feasible_mode 2 only (sf_construct_list_k_opt,
+ * sf_list_routes_feasible); nothing on the scoring path uses them, as in the stock crate. */
+int32_t sf_list_set_time_windows(sf_ctx* ctx, int32_t descriptor_index, int32_t n_nodes, const int64_t* lo, const int64_t* hi,
+                                 const int64_t* service, const int64_t* travel, int64_t departure);
+/* ≙ route_hooks::feasible on every replica's CURRENT lists: out_flags[n_replicas * n_lists], 1 = feasible.  feasible_mode 1 = capacity
+ * (route demand <= capacity), 2 = capacity + time windows: t = departure; per visit t += travel(prev, v), t = max(t, lo[v]),
+ * t += service[v], t <= hi[v]; a missing leg (the one back to the depot included), a negative service or an i64 overflow makes the
+ * route infeasible.  An empty route is feasible. */
+int32_t sf_list_routes_feasible(sf_ctx* ctx, int32_t descriptor_index, int32_t feasible_mode, int32_t* out_flags);
+/* Which evaluation of the time recurrence feasible_mode 2 takes; a pure query.  out_path (may be NULL): 0 = no windows set, 1 = the
+ * checked lane-serial walk, 2 = the composed wave-wide fold, taken when |departure| + (element_capacity + 1) * (largest finite travel +
+ * largest service) + max |lo|, |hi| < 2^59 so that no intermediate sum can leave i64.  Both give the reference's verdict.  out_last_ran (may
+ * be NULL): the path the last kernel that evaluated the time recurrence reports having taken (1 / 2, written by the kernel), 0 = none since
+ * the tables were set. */
+int32_t sf_list_time_window_path(sf_ctx* ctx, int32_t descriptor_index, int32_t* out_path, int32_t* out_last_ran);
+/* For measurements and tests: force_walk != 0 = feasible_mode 2 takes the checked walk whatever the range check says, 0 = it follows the
+ * range check again.  The composed fold cannot be forced (it is exact only on data the check admits). */
+int32_t sf_list_force_time_window_walk(sf_ctx* ctx, int32_t descriptor_index, int32_t force_walk);
 
 /* ≙ ListConstructionPhase, the round-robin list construction (crates/solverforge-solver/src/manager/phase_factory/
  * list_construction/round_robin.rs; kernel round_robin/kernel.rs:71-175).  elements[n] = the declared elements in source order
@@ -637,8 +666,9 @@ int32_t sf_construct_list_round_robin(sf_ctx* ctx, int32_t descriptor_index, con
  * insertion when the routes outnumber the empty owners; when the reference leaves the lists untouched (no empty owner, nothing to
  * route, unmatched routes that cannot be completed) so does the replica.  out_committed[n_replicas] (may be NULL): 1 = routes
  * committed.  Commits the score of the resulting lists; out_scores[n_replicas * score_levels] may be NULL.  Owner-restricted
- * elements (element_owner_fn), per-owner depots / metric classes / capacities and time windows are not modelled
- * (SF_ERR_UNSUPPORTED where detectable).  Solver counters are not advanced. */
+ * elements (element_owner_fn) and per-owner depots / metric classes / capacities are not modelled (SF_ERR_UNSUPPORTED where
+ * detectable).  Time windows play no part here, as in the reference: savings_hooks::feasible (helpers.rs:75-87) does not read them, so
+ * a model with windows is constructed exactly as one without.  Solver counters are not advanced. */
 int32_t sf_construct_list_clarke_wright(sf_ctx* ctx, int32_t descriptor_index, const uint32_t* elements, int32_t n, int32_t feasible_mode,
                                         int64_t* out_scores, int32_t* out_committed);
 

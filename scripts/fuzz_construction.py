@@ -1,7 +1,7 @@
 """Randomised differential run of the list construction phases: random CVRP instances (sizes, capacities from generous to
 impossible, asymmetric / unreachable / tied legs, negative and over-capacity demands) x a random partial start state x a random
 sequence of phases (Clarke-Wright in either feasibility mode, round robin with order keys / owner hook values, ListKOpt under a
-sweep bound, cheapest insertion, regret insertion) on the GPU vs the CPU oracle: lists, committed scores and verdicts after every phase, then a few
+sweep bound (feasibility modes 0 / 1 / 2, mode 2 with time windows laid along the current routes), cheapest insertion, regret insertion) on the GPU vs the CPU oracle: lists, committed scores and verdicts after every phase, then a few
 local-search steps from the constructed state.  Prints one JSON line; `failures` lists the seeds whose runs diverged (none
 expected).  Usage: fuzz_construction.py <seconds> [first_seed]"""
 import json, os, sys, time, traceback
@@ -66,7 +66,27 @@ def run_case(seed):
             sc = d.construct_list_round_robin(0, p["customers"], ks, ow)
             o.construct_list_round_robin([int(p["customers"][i]) for i in miss], None if ks is None else ks[miss], None if ow is None else ow[miss])
         elif phase == "kopt":
-            mode, sweeps = int(rng.integers(0, 2)), int(rng.choice([1, 3, 50]))
+            mode, sweeps = int(rng.integers(0, 3)), int(rng.choice([1, 3, 50]))
+            if mode == 2:  # windows laid along the routes as they stand now (the recipe of datasets.make_cvrptw), widened by a random slack
+                dim = n + 1
+                travel = p["matrix"] if rng.random() < 0.5 else rng.integers(0, 40, (dim, dim)).astype(np.int64)
+                service = rng.integers(0, 6, dim).astype(np.int64)
+                slack, dep = int(rng.choice([0, 30, 300, 3000])), int(rng.integers(0, 20))
+                lo, hi = np.zeros(dim, np.int64), np.full(dim, 10**9, np.int64)
+                for rt in o.get_lists(0):
+                    t, prev = dep, p["depot"]
+                    for c in rt:
+                        leg = int(travel[prev, c])
+                        t += leg if 0 <= leg < 10**12 else 0
+                        lo[c] = max(0, t - int(rng.integers(0, slack + 1)))
+                        t = max(t, int(lo[c])) + int(service[c])
+                        hi[c] = t + int(rng.integers(0, slack + 1))
+                        prev = c
+                if rng.random() < 0.2:  # outside the host range check: the checked walk
+                    hi[int(rng.integers(0, dim))] = np.iinfo(np.int64).max
+                d.set_time_windows(0, lo, hi, service, travel, dep)
+                o.set_time_windows(lo, hi, service, travel, dep)
+                desc["phases"][-1] = "kopt-tw-" + d.time_window_path(0)
             sc = d.construct_list_k_opt(0, 2, mode, sweeps)
             o.construct_list_k_opt(2, mode, sweeps)
         elif phase == "regret":

@@ -18,6 +18,7 @@
 #include "sf_launch.h"
 #include "sf_construct.hip"
 #include "sf_clarke_wright.hip"
+#include "sf_kopt_tw.hip"
 #include "sf_precedence.hip"
 
 using namespace sf;
@@ -99,6 +100,14 @@ struct sf_ctx {
     ListModel lm{};
     NearbyScalarSource nearby_scalar[2];  // 0 = nearby value candidates (nearby change leaf), 1 = nearby entity candidates (nearby swap leaf)
     int nearby_scalar_dynamic = 0;
+    struct TwSpec {  // sf_list_set_time_windows: host copies until sf_initialize, then the device tables (sf_kopt_tw.hip)
+        bool set = false, uploaded = false, force_walk = false, gate_ok = false;
+        int desc = -1, n = 0;
+        std::vector<int64_t> lo, hi, service, travel;
+        int64_t departure = 0;
+        int64_t *d_lo = nullptr, *d_hi = nullptr, *d_service = nullptr, *d_travel = nullptr;
+        int32_t* d_ran = nullptr;  // the path the last mode-2 kernel took, written by the kernel (sf_list_time_window_path)
+    } tw;
     PrecSpec prec;          // ListPrecedenceMakespanConstraint on the list class (sf_precedence.h)
     PrecModel pm{};
     bool prec_policy = false;  // sf_list_set_precedence_policy
@@ -1325,6 +1334,50 @@ static int run_evaluate_all(sf_ctx* ctx, int64_t* out, int commit, int64_t* d_pa
     return SF_OK;
 }
 
+// Time-window tables of the list class's route owner (sf_list_set_time_windows): host copies -> device, replacing an earlier set, and the
+// host range check that admits the composed evaluation (sf_kopt_tw.hip): with T = the largest finite travel entry and S = the largest
+// non-negative service,  |departure| + (n_cap + 1) (T + S) + max |lo|, |hi| < 2^59  keeps every sum of the composed maps inside i64 (a
+// route has at most n_cap visits and one leg more).  Non-finite legs and negative services need no gate: they make a route infeasible on
+// either path.
+static int tw_upload(sf_ctx* ctx) {
+    auto& tw = ctx->tw;
+    const ListModel& m = ctx->lm;
+    if (!ctx->has_list_model || tw.desc != ctx->list_desc) return fail(ctx, SF_ERR_INVALID, "time windows need the list variable's class");
+    if (tw.n != m.dim) return fail(ctx, SF_ERR_INVALID, "time windows: n_nodes must equal the list variable's element id bound (the matrix dimension when a matrix is attached)");
+    const size_t n = (size_t)tw.n;
+    for (int64_t** p : {&tw.d_lo, &tw.d_hi, &tw.d_service, &tw.d_travel}) {
+        if (!*p) continue;
+        auto it = std::find(ctx->allocs.begin(), ctx->allocs.end(), (void*)*p);
+        if (it != ctx->allocs.end()) ctx->allocs.erase(it);
+        (void)hipFree(*p);
+        *p = nullptr;
+    }
+    tw.uploaded = false;
+    int rc;
+    if (!tw.d_ran && (rc = dalloc(ctx, &tw.d_ran, 1))) return rc;
+    HIPCHK(ctx, hipMemsetAsync(tw.d_ran, 0, 4, ctx->stream));
+    if ((rc = upload(ctx, &tw.d_lo, tw.lo.data(), n))) return rc;
+    if ((rc = upload(ctx, &tw.d_hi, tw.hi.data(), n))) return rc;
+    if ((rc = upload(ctx, &tw.d_service, tw.service.data(), n))) return rc;
+    if ((rc = upload(ctx, &tw.d_travel, tw.travel.data(), n * n))) return rc;
+    const auto mag = [](int64_t v) { return v < 0 ? -(__int128)v : (__int128)v; };
+    __int128 max_t = 0, max_s = 0, max_w = 0;
+    for (int64_t v : tw.travel)
+        if (v >= 0 && v != UNREACHABLE && v > max_t) max_t = v;
+    for (int64_t v : tw.service)
+        if (v > max_s) max_s = v;
+    for (size_t i = 0; i < n; ++i) max_w = std::max(max_w, std::max(mag(tw.lo[i]), mag(tw.hi[i])));
+    const __int128 bound = mag(tw.departure) + ((__int128)m.n_cap + 1) * (max_t + max_s) + max_w;
+    tw.gate_ok = bound < (__int128)TW_GATE;
+    tw.uploaded = true;
+    std::vector<int64_t>().swap(tw.lo), std::vector<int64_t>().swap(tw.hi), std::vector<int64_t>().swap(tw.service), std::vector<int64_t>().swap(tw.travel);
+    return SF_OK;
+}
+static TwTables tw_tables(const sf_ctx* ctx) {
+    const auto& tw = ctx->tw;
+    return TwTables{tw.d_lo, tw.d_hi, tw.d_service, tw.d_travel, tw.departure, (tw.gate_ok && !tw.force_walk) ? 1 : 0, tw.d_ran};
+}
+
 extern "C" {
 
 int32_t sf_initialize(sf_ctx* ctx, int64_t* out_scores) {
@@ -1364,6 +1417,7 @@ int32_t sf_initialize(sf_ctx* ctx, int64_t* out_scores) {
             ctx->xown_weight = cs.weight;
             if ((rc = dalloc(ctx, &ctx->d_xown_tab, (size_t)ctx->R * ctx->sm.n))) return rc;
         }
+        if (ctx->tw.set && (rc = tw_upload(ctx))) return rc;
         ctx->initialized = true;
     }
     return run_evaluate_all(ctx, out_scores, 1);
@@ -2214,26 +2268,102 @@ int32_t sf_construct_list_k_opt(sf_ctx* ctx, int32_t descriptor_index, int32_t k
     if (ctx && ctx->xown_level >= 0) return fail(ctx, SF_ERR_UNSUPPORTED, "sf_construct_list_k_opt: a model with the join of its two planning classes is searched by the fused engine only");
     if (!ctx || !ctx->initialized) return fail(ctx, SF_ERR_INVALID, "sf_initialize first");
     if (!ctx->has_list_model || descriptor_index != ctx->list_desc) return fail(ctx, SF_ERR_INVALID, "list k-opt needs the list variable's class");
-    if (feasible_mode != 0 && feasible_mode != 1) return fail(ctx, SF_ERR_INVALID, "feasible_mode: 0 no feasibility hook, 1 capacity");
+    if (feasible_mode < 0 || feasible_mode > 2) return fail(ctx, SF_ERR_INVALID, "feasible_mode: 0 no feasibility hook, 1 capacity, 2 capacity + time windows");
     if (max_sweeps < 1) return fail(ctx, SF_ERR_INVALID, "max_sweeps must be >= 1 (the termination policy of the phase)");
     if (ctx->lm.n_cap > 65535 || ctx->lm.dim > 65536) return fail(ctx, SF_ERR_UNSUPPORTED, "construction packs list elements in 16 bits");
     if (ctx->pm.on) return fail(ctx, SF_ERR_UNSUPPORTED, "list k-opt on a model with precedence hooks");
     if (!ctx->lm.mat) return fail(ctx, SF_ERR_UNSUPPORTED, "list k-opt needs the distance matrix (route_distance)");
-    if (feasible_mode == 1 && !ctx->lm.demand) return fail(ctx, SF_ERR_INVALID, "capacity feasibility needs the demand column");
+    if (feasible_mode >= 1 && !ctx->lm.demand) return fail(ctx, SF_ERR_INVALID, "capacity feasibility needs the demand column");
+    if (feasible_mode == 2 && !ctx->tw.uploaded) return fail(ctx, SF_ERR_INVALID, "feasible_mode 2 needs the time windows (sf_list_set_time_windows)");
     int rc = alloc_search(ctx);
     if (rc) return rc;
     if (k == 2 && ctx->lm.V > 0) {  // only k = 2 is implemented by the reference: every other value is a scored no-op (kernel.rs:69-77)
         const size_t lds = align_up((size_t)ctx->lm.n_cap * 2, 16) + 16;
         if (lds > SF_LDS_BUDGET) return fail(ctx, SF_ERR_UNSUPPORTED, "a route does not fit one wave's LDS slice");
-        hipError_t e = hipFuncSetAttribute((const void*)k_list_construct_two_opt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const dim3 grid((unsigned)ctx->lm.V, (unsigned)ctx->R);
+        // the complete hook is a kernel of its own (sf_kopt_tw.hip); modes 0 / 1 launch the instantiation they always did
+        const void* kern = feasible_mode == 2 ? (const void*)k_list_construct_two_opt_tw : (const void*)k_list_construct_two_opt;
+        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_list_construct_two_opt, dim3((unsigned)ctx->lm.V, (unsigned)ctx->R), dim3(64), lds, ctx->stream, ctx->lm, feasible_mode, max_sweeps, ctx->sp.stats);
+            if (feasible_mode == 2)
+                hipLaunchKernelGGL(k_list_construct_two_opt_tw, grid, dim3(64), lds, ctx->stream, ctx->lm, tw_tables(ctx), max_sweeps, ctx->sp.stats);
+            else
+                hipLaunchKernelGGL(k_list_construct_two_opt, grid, dim3(64), lds, ctx->stream, ctx->lm, feasible_mode, max_sweeps, ctx->sp.stats);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) return fail(ctx, SF_ERR_HIP, hipGetErrorString(e));
     }
     return run_evaluate_all(ctx, out_scores, 1);
+}
+
+// ≙ ProblemData{time_windows, service_durations, travel_times, vehicle_departure_time} (solverforge-cvrp problem_data.rs:20-23).  Values are
+// data, never refused: what the reference's recurrence makes of them (infeasible routes) is what the device makes of them.
+int32_t sf_list_set_time_windows(sf_ctx* ctx, int32_t descriptor_index, int32_t n_nodes, const int64_t* lo, const int64_t* hi, const int64_t* service,
+                                 const int64_t* travel, int64_t departure) {
+    DeviceGuard _dev(ctx);
+    if (!ctx) return SF_ERR_INVALID;
+    if (!ctx->classes.count(descriptor_index) || !ctx->classes[descriptor_index].has_list)
+        return fail(ctx, SF_ERR_INVALID, "sf_list_set_time_windows: declare the list variable first");
+    if (!lo || !hi || !service || !travel) return fail(ctx, SF_ERR_INVALID, "sf_list_set_time_windows: null array");
+    const int32_t want = ctx->initialized ? ctx->lm.dim : ctx->classes[descriptor_index].element_bound;
+    if (ctx->initialized ? n_nodes != want : n_nodes < want || n_nodes < 1)
+        return fail(ctx, SF_ERR_INVALID, "sf_list_set_time_windows: n_nodes must equal the list variable's element id bound (the matrix dimension when a matrix is attached)");
+    auto& tw = ctx->tw;
+    const size_t n = (size_t)n_nodes;
+    tw.lo.assign(lo, lo + n), tw.hi.assign(hi, hi + n), tw.service.assign(service, service + n), tw.travel.assign(travel, travel + n * n);
+    tw.departure = departure, tw.n = n_nodes, tw.desc = descriptor_index, tw.set = true;
+    return ctx->initialized ? tw_upload(ctx) : SF_OK;
+}
+
+// ≙ route_hooks::feasible (helpers.rs:109-119) on every replica's committed lists
+int32_t sf_list_routes_feasible(sf_ctx* ctx, int32_t descriptor_index, int32_t feasible_mode, int32_t* out_flags) {
+    DeviceGuard _dev(ctx);
+    if (!ctx || !ctx->initialized) return fail(ctx, SF_ERR_INVALID, "sf_initialize first");
+    if (!ctx->has_list_model || descriptor_index != ctx->list_desc) return fail(ctx, SF_ERR_INVALID, "sf_list_routes_feasible needs the list variable's class");
+    if (!out_flags) return fail(ctx, SF_ERR_INVALID, "sf_list_routes_feasible: null argument");
+    if (feasible_mode != 1 && feasible_mode != 2) return fail(ctx, SF_ERR_INVALID, "feasible_mode: 1 capacity, 2 capacity + time windows");
+    if (!ctx->lm.demand) return fail(ctx, SF_ERR_INVALID, "capacity feasibility needs the demand column");
+    if (feasible_mode == 2 && !ctx->tw.uploaded) return fail(ctx, SF_ERR_INVALID, "feasible_mode 2 needs the time windows (sf_list_set_time_windows)");
+    if (ctx->lm.V == 0) return SF_OK;
+    const size_t n = (size_t)ctx->R * ctx->lm.V;
+    int32_t* d_out = nullptr;
+    hipError_t e = hipMalloc((void**)&d_out, n * 4);
+    if (e != hipSuccess) return fail(ctx, SF_ERR_HIP, hipGetErrorString(e));
+    hipLaunchKernelGGL(k_list_routes_feasible, dim3((unsigned)ctx->lm.V, (unsigned)ctx->R), dim3(64), 0, ctx->stream, ctx->lm, tw_tables(ctx), feasible_mode, d_out);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out_flags, d_out, n * 4, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d_out);
+    if (e != hipSuccess) return fail(ctx, SF_ERR_HIP, hipGetErrorString(e));
+    return SF_OK;
+}
+
+// Which evaluation of the time recurrence feasible_mode 2 takes.  A pure query: out_path 0 = no windows set, 1 = the checked lane-serial walk,
+// 2 = the composed wave-wide fold (the host range check of the tables passed and the walk is not forced); out_last_ran = the path the last
+// mode-2 kernel of this context reports having taken (written by the kernel itself), 0 = none has run since the tables were set.
+int32_t sf_list_time_window_path(sf_ctx* ctx, int32_t descriptor_index, int32_t* out_path, int32_t* out_last_ran) {
+    DeviceGuard _dev(ctx);
+    if (!ctx || !ctx->initialized) return fail(ctx, SF_ERR_INVALID, "sf_initialize first");
+    if (!ctx->has_list_model || descriptor_index != ctx->list_desc) return fail(ctx, SF_ERR_INVALID, "sf_list_time_window_path needs the list variable's class");
+    if (out_path) *out_path = !ctx->tw.uploaded ? 0 : (ctx->tw.gate_ok && !ctx->tw.force_walk) ? 2 : 1;
+    if (out_last_ran) {
+        *out_last_ran = 0;
+        if (ctx->tw.uploaded) {
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            HIPCHK(ctx, hipMemcpy(out_last_ran, ctx->tw.d_ran, 4, hipMemcpyDeviceToHost));
+        }
+    }
+    return SF_OK;
+}
+
+// force_walk != 0: feasible_mode 2 takes the checked walk whatever the range check of the tables says; 0: it follows the range check again.
+// (The composed fold cannot be forced: it is exact only on data the check admits.)  For measurements and tests; both paths give the reference's verdict.
+int32_t sf_list_force_time_window_walk(sf_ctx* ctx, int32_t descriptor_index, int32_t force_walk) {
+    if (!ctx || !ctx->initialized) return fail(ctx, SF_ERR_INVALID, "sf_initialize first");
+    if (!ctx->has_list_model || descriptor_index != ctx->list_desc) return fail(ctx, SF_ERR_INVALID, "sf_list_force_time_window_walk needs the list variable's class");
+    ctx->tw.force_walk = force_walk != 0;
+    return SF_OK;
 }
 
 // ≙ ListConstructionPhase (round robin) over every replica's current lists (csrc/sf_construct.hip)

@@ -58,6 +58,38 @@ def make_cvrp(n_customers=1000, n_vehicles=100, capacity=55, seed=0, coord_range
     }
 
 
+def make_cvrptw(n_customers=1000, n_vehicles=100, capacity=55, seed=0, slack=1000, tw_seed=1, lo_slack=None, one_route=False,
+                departure=0, coord_range=1000):
+    """make_cvrp plus ProblemData's time windows, laid along the START routes so that every start route is time-feasible:
+    travel = the distance matrix, service = 0..5 per customer (0 at the depot); walking each start route from `departure`, a
+    visit's window opens up to `lo_slack` (default `slack`) before the arrival (never below 0) and closes up to `slack` after the end
+    of its service.  lo_slack = 0: every window opens at the start route's arrival time, so waiting binds as soon as a visit is
+    reached earlier.  one_route: all customers in the first route, in customer order.  Nodes off every route (the depot) keep
+    [0, 10^9].  Draws come from `stream(tw_seed ^ 0x7457, ...)`: service, then the lo draw and the hi draw per node."""
+    p = make_cvrp(n_customers, n_vehicles, capacity, seed, coord_range)
+    dim = n_customers + 1
+    if one_route:
+        p["routes"] = [[int(c) for c in p["customers"]]] + [[] for _ in range(n_vehicles - 1)]
+    lo_slack = slack if lo_slack is None else lo_slack
+    r = stream(tw_seed ^ 0x7457, 3 * dim)
+    service = (r[0:dim] % np.uint64(6)).astype(np.int64)
+    service[0] = 0
+    d_lo = (r[dim:2 * dim] % np.uint64(lo_slack + 1)).astype(np.int64)
+    d_hi = (r[2 * dim:3 * dim] % np.uint64(slack + 1)).astype(np.int64)
+    travel = p["matrix"].copy()
+    lo, hi = np.zeros(dim, np.int64), np.full(dim, 10**9, np.int64)
+    for rt in p["routes"]:
+        t, prev = int(departure), p["depot"]
+        for v in rt:
+            t += int(travel[prev, v])
+            lo[v] = max(0, t - int(d_lo[v]))
+            t = max(t, int(lo[v])) + int(service[v])
+            hi[v] = t + int(d_hi[v])
+            prev = v
+    p.update(time_windows=(lo, hi), service=service, travel=travel, departure=int(departure))
+    return p
+
+
 def make_graph(n=10000, n_edges=100000, n_colors=16, seed=0):
     """C2: n nodes, n_edges distinct undirected edges (i<j uniform, reject dup/self),
     neighbours symmetric + sorted; colours start unassigned."""

@@ -425,11 +425,41 @@ class GpuScoreDirector:
 
     def construct_list_k_opt(self, descriptor_index, k=2, feasible_mode=1, max_sweeps=1000):
         """≙ ListKOptPhase on every replica: every route swept to its 2-opt local optimum (k = 2; other k: scored no-op), at
-        most max_sweeps sweeps per route; feasible_mode 0 = no feasibility hook, 1 = capacity.  Returns the committed scores
-        [n_replicas, levels]."""
+        most max_sweeps sweeps per route; feasible_mode 0 = no feasibility hook, 1 = capacity, 2 = capacity + the time windows of
+        set_time_windows (a reversal whose route would arrive after a window has closed is not taken).  Returns the committed
+        scores [n_replicas, levels]."""
         out = np.zeros((self.n_replicas, self.levels), dtype=np.int64)
         check(self._L.sf_construct_list_k_opt(self._h, descriptor_index, int(k), int(feasible_mode), int(max_sweeps), ptr(out)), self._h)
         return out
+
+    def set_time_windows(self, descriptor_index, lo, hi, service, travel, departure=0):
+        """≙ ProblemData{time_windows, service_durations, travel_times, vehicle_departure_time} of the list class's route owner:
+        lo / hi / service per node, travel [n_nodes, n_nodes], all int64 in the caller's node ids.  Valid once the list variable
+        is declared, before or after initialize(); a second call replaces the first.  Values are data, not range-checked."""
+        lo, hi, service = (np.ascontiguousarray(a, dtype=np.int64) for a in (lo, hi, service))
+        travel = np.ascontiguousarray(travel, dtype=np.int64)
+        n = len(lo)
+        if lo.ndim != 1 or len(hi) != n or len(service) != n or travel.shape != (n, n):
+            raise SolverForgeError("time windows: lo / hi / service [n_nodes] and travel [n_nodes, n_nodes]")
+        check(self._L.sf_list_set_time_windows(self._h, descriptor_index, n, ptr(lo), ptr(hi), ptr(service), ptr(travel), int(departure)), self._h)
+
+    def routes_feasible(self, descriptor_index, feasible_mode=2):
+        """≙ route_hooks::feasible on every replica's current lists: int32 [n_replicas, n_lists], 1 = feasible; feasible_mode 1 =
+        capacity, 2 = capacity + time windows.  An empty route is feasible."""
+        out = np.zeros((self.n_replicas, self._entity_counts[descriptor_index]), dtype=np.int32)
+        check(self._L.sf_list_routes_feasible(self._h, descriptor_index, int(feasible_mode), ptr(out)), self._h)
+        return out
+
+    def time_window_path(self, descriptor_index, force_walk=None, last_ran=False):
+        """Which evaluation of the time recurrence feasible_mode 2 takes: "none" (no windows set), "walk" (the checked lane-serial
+        walk) or "composed" (the wave-wide fold, when the host range check of the tables passed).  force_walk True / False first
+        switches the override that takes the checked walk whatever the range check says (sf_list_force_time_window_walk).
+        last_ran=True returns instead what the last kernel that evaluated the recurrence reports having taken."""
+        if force_walk is not None:
+            check(self._L.sf_list_force_time_window_walk(self._h, descriptor_index, int(bool(force_walk))), self._h)
+        p, ran = C.c_int32(0), C.c_int32(0)
+        check(self._L.sf_list_time_window_path(self._h, descriptor_index, C.byref(p), C.byref(ran)), self._h)
+        return ("none", "walk", "composed")[ran.value if last_ran else p.value]
 
     def construct_list_round_robin(self, descriptor_index, elements, order_keys=None, owners=None):
         """≙ ListConstructionPhase (round robin) on every replica: the elements of `elements` (source order) that are in no list

@@ -16,7 +16,8 @@ def build_cvrp(problem, n_replicas=1, device_id=0, max_nearby=20, leaves=("nearb
     vehicle_capacity (uni on routes, max(0, load-cap) hard), total_distance (uni on routes,
     depot->...->depot, soft); leaves = default list policy nearby change + nearby swap with
     MatrixDistanceMeter, max_nearby 20 (default_local_search/policy/list.rs:19,97-141).
-    weights = the three constraints' weights in that order (the model's own are 1, 1, 1)."""
+    weights = the three constraints' weights in that order (the model's own are 1, 1, 1).  A problem that carries `time_windows` (lo, hi),
+    `service`, `travel` and optionally `departure` hands them over for feasible_mode 2 of construct_list_k_opt / routes_feasible."""
     d = GpuScoreDirector(score_levels=2, hard_levels=1, n_replicas=n_replicas, device_id=device_id)
     n_vehicles = len(problem["routes"])
     dim = problem["matrix"].shape[0]
@@ -54,6 +55,10 @@ def build_cvrp(problem, n_replicas=1, device_id=0, max_nearby=20, leaves=("nearb
             d.add_ruin_selector(0, min_ruin_count=ruin[0], max_ruin_count=ruin[1], moves_per_step=ruin[2], variable_name="visits")
         else:
             raise ValueError(f"unknown leaf {leaf!r}")
+    # ProblemData's time windows (datasets.make_cvrptw): read by feasible_mode 2 of the route-local 2-opt only, never by the score
+    if "time_windows" in problem:
+        lo, hi = problem["time_windows"]
+        d.set_time_windows(0, lo, hi, problem["service"], problem["travel"], int(problem.get("departure", 0)))
     return d
 
 
