@@ -227,6 +227,28 @@ static int upload(sf_ctx* ctx, T** out, const T* src, size_t n) {
     return SF_OK;
 }
 
+// a HIP status as the entry points that a host drives call by call report it
+static int hip_rc(sf_ctx* ctx, hipError_t e) { return e == hipSuccess ? SF_OK : fail(ctx, SF_ERR_HIP, hipGetErrorString(e)); }
+
+// Device scratch of ONE call (dalloc / upload above are for memory that lives as long as the context): the entry point declares what it
+// needs, and every return frees it.  Nothing is pooled or kept for the next call.  hipFree waits for the device, so a return that leaves a
+// kernel queued on the buffer (a refusal found after the first launches) is safe without a synchronize of its own.
+template <class T>
+struct Scratch {
+    T* p = nullptr;
+    Scratch() = default;
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch() { (void)hipFree(p); }
+    int alloc(sf_ctx* ctx, size_t n) {  // n elements, at least one
+        return hip_rc(ctx, hipMalloc((void**)&p, (n ? n : 1) * sizeof(T)));
+    }
+    int upload(sf_ctx* ctx, const T* src, size_t n) {  // ... filled from the host on the context's stream
+        if (int rc = alloc(ctx, n)) return rc;
+        return n ? hip_rc(ctx, hipMemcpyAsync(p, src, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream)) : SF_OK;
+    }
+};
+
 extern "C" {
 
 int32_t sf_device_count(void) {
@@ -1515,987 +1537,6 @@ int32_t sf_get_scores(sf_ctx* ctx, int64_t* out_scores) {
     return download_scores(ctx, ctx->has_list_model ? ctx->lm.score : ctx->sm.score, out_scores);
 }
 
-// SF_MOVE_LIST_RUIN entries of a host batch: one wavefront each (csrc/sf_construct.hip)
-static hipError_t launch_ruin_moves(sf_ctx* ctx, int replica, const int32_t* d_moves, const std::vector<int32_t>& which, int64_t* d_sc, int32_t* d_do,
-                                    int commit) {
-    const SelectorSpec* rs = ruin_selector(ctx);
-    const int skip_empty = rs ? rs->skip_empty : 0;
-    int32_t* d_idx = nullptr;
-    hipError_t e = hipMalloc((void**)&d_idx, which.size() * 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_idx, which.data(), which.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-    const RuinMoveCarve cv(ctx->lm.V, ctx->lm.n_cap);
-    if (e == hipSuccess) {
-        if (ctx->levels <= 2) {
-            auto kern = k_list_ruin_moves<2>;
-            e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv.total);
-            if (e == hipSuccess)
-                hipLaunchKernelGGL(kern, dim3((unsigned)which.size()), dim3(64), cv.total, ctx->stream, ctx->lm, replica, d_moves, d_idx, d_sc, d_do, skip_empty, commit);
-        } else {
-            auto kern = k_list_ruin_moves<4>;
-            e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv.total);
-            if (e == hipSuccess)
-                hipLaunchKernelGGL(kern, dim3((unsigned)which.size()), dim3(64), cv.total, ctx->stream, ctx->lm, replica, d_moves, d_idx, d_sc, d_do, skip_empty, commit);
-        }
-    }
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_idx);
-    return e;
-}
-
-// SF_MOVE_LIST_RUIN records on a precedence model: k_prec_ruin_moves, at most R records per launch (one scratch slot each)
-static int ensure_plf(sf_ctx* ctx);
-static int launch_prec_ruin_moves(sf_ctx* ctx, int replica, const int32_t* d_moves, const std::vector<int32_t>& which, int64_t* d_sc, int32_t* d_do, int commit) {
-    if (ctx->lm.dist_level >= 0 || ctx->lm.cap_level >= 0)
-        return fail(ctx, SF_ERR_UNSUPPORTED, "list ruin move on a precedence model with distance / capacity constraints");
-    if (int rc = ensure_plf(ctx)) return rc;
-    const size_t lds = (((size_t)ctx->lm.V + 1 + 3) & ~(size_t)3) * 4 + (size_t)ctx->lm.n_cap * 2 + 16;
-    if (ctx->lm.n_cap > 65535 || lds > SF_LDS_BUDGET) return fail(ctx, SF_ERR_UNSUPPORTED, "list ruin moves: the list class must fit one wave's LDS slice with 16-bit elements");
-    const SelectorSpec* rs = ruin_selector(ctx);
-    const int skip_empty = rs ? rs->skip_empty : 0;
-    const int lvl_order = ctx->pm.hard_level < ctx->pm.mk_level ? 0 : (ctx->pm.hard_level > ctx->pm.mk_level ? 1 : 2);
-    int32_t* d_idx = nullptr;
-    hipError_t e = hipMalloc((void**)&d_idx, which.size() * 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_idx, which.data(), which.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_prec_ruin_moves, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    for (size_t base = 0; base < which.size() && e == hipSuccess; base += (size_t)ctx->R) {
-        const unsigned chunk = (unsigned)std::min<size_t>((size_t)ctx->R, which.size() - base);
-        hipLaunchKernelGGL(k_prec_ruin_moves, dim3(chunk), dim3(64), lds, ctx->stream, ctx->lm, ctx->pm, ctx->plf, replica, d_moves, d_idx + base, d_sc, d_do, commit,
-                           lvl_order, ctx->prec_policy ? 1 : 0, skip_empty);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_idx);
-    if (e != hipSuccess) return fail(ctx, SF_ERR_HIP, hipGetErrorString(e));
-    return SF_OK;
-}
-
-int32_t sf_step_evaluate(sf_ctx* ctx, int32_t replica, const sf_move_t* moves, int64_t n, int64_t* out_scores,
-                         int32_t* out_doable) {
-    DeviceGuard _dev(ctx);
-    if (!ctx || !ctx->initialized) return fail(ctx, SF_ERR_INVALID, "sf_initialize first");
-    if (replica < 0 || replica >= ctx->R || n < 0 || !moves || !out_scores || !out_doable)
-        return fail(ctx, SF_ERR_INVALID, "bad sf_step_evaluate arguments");
-    if (ctx->xown_level >= 0)
-        for (int64_t i = 0; i < n; ++i)
-            if (moves[i].kind == SF_MOVE_LIST_RUIN) return fail(ctx, SF_ERR_UNSUPPORTED, "the join of the two planning classes is not priced by a ruin's recreate");
-    if (n == 0) return SF_OK;
-    // one allocation per call, released on every path (hipFree(nullptr) is a no-op)
-    int32_t* d_moves = nullptr;
-    int64_t* d_sc = nullptr;
-    int32_t* d_do = nullptr;
-    auto release = [&]() {
-        (void)hipFree(d_moves);
-        (void)hipFree(d_sc);
-        (void)hipFree(d_do);
-    };
-    hipError_t ea = hipMalloc((void**)&d_moves, (size_t)n * 24);
-    if (ea == hipSuccess) ea = hipMalloc((void**)&d_sc, (size_t)n * ctx->levels * 8);
-    if (ea == hipSuccess) ea = hipMalloc((void**)&d_do, (size_t)n * 4);
-    if (ea == hipSuccess) ea = hipMemcpyAsync(d_moves, moves, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream);
-    if (ea != hipSuccess) {
-        release();
-        return fail(ctx, SF_ERR_HIP, hipGetErrorString(ea));
-    }
-    int grid = (int)((n + 255) / 256);
-    const int mixed = ctx->has_list_model && ctx->has_scalar_model;
-    if (mixed) {
-        (void)hipMemsetAsync(d_sc, 0, (size_t)n * ctx->levels * 8, ctx->stream);
-        (void)hipMemsetAsync(d_do, 0, (size_t)n * 4, ctx->stream);
-    }
-    if (ctx->has_list_model)
-        hipLaunchKernelGGL(k_list_evaluate_moves, dim3(grid), dim3(256), 0, ctx->stream, ctx->lm, replica, d_moves, n, d_sc, d_do, mixed);
-    if (ctx->has_scalar_model)
-        hipLaunchKernelGGL(k_scalar_evaluate_moves, dim3(grid), dim3(256), scalar_table_bytes(ctx), ctx->stream, ctx->sm, replica, d_moves, n, d_sc, d_do, mixed);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && ctx->has_list_model) {  // list ruin moves: scored by their own kernel, one wavefront per move
-        std::vector<int32_t> which;
-        for (int64_t i = 0; i < n; ++i)
-            if (moves[i].kind == SF_MOVE_LIST_RUIN) which.push_back((int32_t)i);
-        if (!which.empty() && ctx->pm.on) {  // precedence model: the recreate is scored by the precedence constraint (k_prec_ruin_moves)
-            const int rc2 = launch_prec_ruin_moves(ctx, replica, d_moves, which, d_sc, d_do, 0);
-            if (rc2) {
-                release();
-                return rc2;
-            }
-        } else if (!which.empty()) {
-            if (ctx->lm.n_cap > 65535 || ctx->lm.dim > 65536 || RuinMoveCarve(ctx->lm.V, ctx->lm.n_cap).total > SF_LDS_BUDGET) {
-                release();
-                return fail(ctx, SF_ERR_UNSUPPORTED, "list ruin moves: the list class must fit one wave's LDS slice with 16-bit elements");
-            }
-            e = launch_ruin_moves(ctx, replica, d_moves, which, d_sc, d_do, 0);
-        }
-    }
-    if (e == hipSuccess && ctx->has_list_model && ctx->pm.on) {  // precedence delta of every doable list move: one wavefront per record
-        const PrecMoveCarve cv(ctx->lm.V, ctx->lm.n_cap);
-        if (ctx->lm.n_cap > 65535 || cv.total > SF_LDS_BUDGET) {
-            release();
-            return fail(ctx, SF_ERR_UNSUPPORTED, "list precedence moves: the list class must fit one wave's LDS slice with 16-bit elements");
-        }
-        e = hipFuncSetAttribute((const void*)k_prec_evaluate_moves, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv.total);
-        for (int64_t base = 0; base < n && e == hipSuccess; base += ctx->R) {
-            const int chunk = (int)std::min<int64_t>(ctx->R, n - base);
-            hipLaunchKernelGGL(k_prec_evaluate_moves, dim3(chunk), dim3(64), cv.total, ctx->stream, ctx->lm, ctx->pm, replica, d_moves, base, d_sc, d_do);
-            e = hipGetLastError();
-        }
-    }
-    if (e == hipSuccess && ctx->xown_level >= 0) {  // the join of the two planning classes: its delta from the move's coordinates (k_cross_owner_evaluate_moves)
-        hipLaunchKernelGGL(k_cross_owner_holders, dim3(1), dim3(256), 0, ctx->stream, ctx->lm, replica, ctx->sm.n, ctx->d_xown_tab);
-        hipLaunchKernelGGL(k_cross_owner_evaluate_moves, dim3(grid), dim3(256), 0, ctx->stream, ctx->lm, ctx->sm.vals, ctx->sm.n, ctx->d_xown_tab, replica, d_moves, n,
-                           ctx->xown_level, ctx->xown_weight, d_sc, d_do);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out_scores, d_sc, (size_t)n * ctx->levels * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_doable, d_do, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    release();
-    if (e != hipSuccess) return fail(ctx, SF_ERR_HIP, hipGetErrorString(e));
-    return SF_OK;
-}
-
-static int xown_price(sf_ctx* ctx, int32_t replica, const sf_move_t* records, int64_t n_records, const int64_t* compound_offsets);
-static void xown_commit(sf_ctx* ctx, int32_t replica);
-// ScalarCandidateProvider surface: multi-edit candidates scored as ONE CompoundScalarMove each
-int32_t sf_step_evaluate_compound(sf_ctx* ctx, int32_t replica, const sf_move_t* edits, const int64_t* offsets, int64_t n,
-                                  int64_t* out_scores, int32_t* out_doable) {
-    DeviceGuard _dev(ctx);
-    if (!ctx || !ctx->initialized) return fail(ctx, SF_ERR_INVALID, "sf_initialize first");
-    if (!ctx->has_scalar_model) return fail(ctx, SF_ERR_INVALID, "compound scalar candidates need a scalar variable");
-    if (replica < 0 || replica >= ctx->R || n < 0 || !offsets || !out_scores || !out_doable)
-        return fail(ctx, SF_ERR_INVALID, "bad sf_step_evaluate_compound arguments");
-    if (ctx->sm.grp_level >= 0 && ctx->sm.grp_mode >= 1)
-        return fail(ctx, SF_ERR_UNSUPPORTED, "compound candidates on a load_balance / balance model (floating-point aggregate) are not chained on the device");
-    if (ctx->sm.run_level >= 0) return fail(ctx, SF_ERR_UNSUPPORTED, "compound candidates on a consecutive-runs model are not chained on the device");
-    if (n == 0) return SF_OK;
-    if (offsets[0] != 0) return fail(ctx, SF_ERR_INVALID, "offsets[0] must be 0");
-    for (int64_t i = 0; i < n; ++i) {
-        if (offsets[i + 1] < offsets[i]) return fail(ctx, SF_ERR_INVALID, "offsets must not decrease");
-        if (offsets[i + 1] - offsets[i] > SF_COMPOUND_MAX) return fail(ctx, SF_ERR_UNSUPPORTED, "at most 8 edits per compound candidate on the device");
-    }
-    const int64_t total = offsets[n];
-    if (total > 0 && !edits) return fail(ctx, SF_ERR_INVALID, "edits is NULL");
-    for (int64_t k = 0; k < total; ++k)
-        if (edits[k].kind != SF_MOVE_CHANGE) return fail(ctx, SF_ERR_INVALID, "a ScalarEdit is a SF_MOVE_CHANGE-shaped record");
-    int32_t* d_edits = nullptr;
-    int64_t *d_off = nullptr, *d_sc = nullptr;
-    int32_t* d_do = nullptr;
-    auto release = [&]() {
-        (void)hipFree(d_edits);
-        (void)hipFree(d_off);
-        (void)hipFree(d_sc);
-        (void)hipFree(d_do);
-    };
-    hipError_t ea = hipMalloc((void**)&d_edits, (size_t)(total > 0 ? total : 1) * 24);
-    if (ea == hipSuccess) ea = hipMalloc((void**)&d_off, (size_t)(n + 1) * 8);
-    if (ea == hipSuccess) ea = hipMalloc((void**)&d_sc, (size_t)n * ctx->levels * 8);
-    if (ea == hipSuccess) ea = hipMalloc((void**)&d_do, (size_t)n * 4);
-    if (ea == hipSuccess && total > 0) ea = hipMemcpyAsync(d_edits, edits, (size_t)total * 24, hipMemcpyHostToDevice, ctx->stream);
-    if (ea == hipSuccess) ea = hipMemcpyAsync(d_off, offsets, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (ea != hipSuccess) {
-        release();
-        return fail(ctx, SF_ERR_HIP, hipGetErrorString(ea));
-    }
-    hipLaunchKernelGGL(k_scalar_evaluate_compound, dim3((int)((n + 255) / 256)), dim3(256), scalar_table_bytes(ctx), ctx->stream, ctx->sm, replica,
-                       d_edits, d_off, n, d_sc, d_do);
-    if (ctx->xown_level >= 0) {  // the join of the two planning classes: a scalar edit changes the A side's key
-        hipLaunchKernelGGL(k_cross_owner_holders, dim3(1), dim3(256), 0, ctx->stream, ctx->lm, replica, ctx->sm.n, ctx->d_xown_tab);
-        hipLaunchKernelGGL(k_cross_owner_evaluate_compound, dim3((int)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->sm.vals, ctx->sm.n, ctx->d_xown_tab, replica, d_edits,
-                           d_off, n, ctx->levels, ctx->xown_level, ctx->xown_weight, d_sc, d_do);
-    }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out_scores, d_sc, (size_t)n * ctx->levels * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_doable, d_do, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    release();
-    if (e != hipSuccess) return fail(ctx, SF_ERR_HIP, hipGetErrorString(e));
-    return SF_OK;
-}
-
-int32_t sf_apply_compound(sf_ctx* ctx, int32_t replica, const sf_move_t* edits, int64_t n_edits) {
-    DeviceGuard _dev(ctx);
-    if (!ctx || !ctx->initialized || !edits || replica < 0 || replica >= ctx->R) return fail(ctx, SF_ERR_INVALID, "bad sf_apply_compound arguments");
-    if (!ctx->has_scalar_model) return fail(ctx, SF_ERR_INVALID, "compound scalar candidates need a scalar variable");
-    if (n_edits <= 0) return fail(ctx, SF_ERR_INVALID, "move is not doable");
-    if (n_edits > SF_COMPOUND_MAX) return fail(ctx, SF_ERR_UNSUPPORTED, "at most 8 edits per compound candidate on the device");
-    if (ctx->sm.grp_level >= 0 && ctx->sm.grp_mode >= 1)
-        return fail(ctx, SF_ERR_UNSUPPORTED, "compound candidates on a load_balance / balance model (floating-point aggregate) are not chained on the device");
-    if (ctx->sm.run_level >= 0) return fail(ctx, SF_ERR_UNSUPPORTED, "compound candidates on a consecutive-runs model are not chained on the device");
-    for (int64_t k = 0; k < n_edits; ++k)
-        if (edits[k].kind != SF_MOVE_CHANGE) return fail(ctx, SF_ERR_INVALID, "a ScalarEdit is a SF_MOVE_CHANGE-shaped record");
-    int rc = alloc_search(ctx);
-    if (rc) return rc;
-    int32_t* d_edits = nullptr;
-    hipError_t ea = hipMalloc((void**)&d_edits, (size_t)n_edits * 24);
-    if (ea == hipSuccess) ea = hipMemcpyAsync(d_edits, edits, (size_t)n_edits * 24, hipMemcpyHostToDevice, ctx->stream);
-    if (ea != hipSuccess) {
-        (void)hipFree(d_edits);
-        return fail(ctx, SF_ERR_HIP, hipGetErrorString(ea));
-    }
-    {
-        const int64_t one_candidate[2] = {0, n_edits};
-        if ((rc = xown_price(ctx, replica, edits, n_edits, one_candidate))) {
-            (void)hipFree(d_edits);
-            return rc;
-        }
-    }
-    hipLaunchKernelGGL(k_scalar_apply_compound, dim3(1), dim3(64), scalar_table_bytes(ctx), ctx->stream, ctx->sm, replica, d_edits, (int)n_edits,
-                       ctx->d_ok);
-    xown_commit(ctx, replica);
-    int32_t ok = 0;
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(&ok, ctx->d_ok, 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_edits);
-    if (e != hipSuccess) return fail(ctx, SF_ERR_HIP, hipGetErrorString(e));
-    if (!ok) return fail(ctx, SF_ERR_INVALID, "move is not doable");
-    return SF_OK;
-}
-
-// One host-driven local-search step over a ScalarCandidateProvider's output (GroupedScalarMoveSelector; see the header).
-int32_t sf_step_decide(sf_ctx* ctx, int32_t replica, const sf_move_t* edits, const int64_t* offsets, int64_t n, int32_t group_name_len,
-                       int64_t max_moves_per_step, int64_t* out_kept, int64_t* out_n_kept, int64_t* out_scores, int32_t* out_flags,
-                       int64_t* out_consumed, int64_t* out_selected) {
-    return sf_step_decide_gated(ctx, replica, edits, offsets, nullptr, n, group_name_len, max_moves_per_step, out_kept, out_n_kept, out_scores, out_flags,
-                                out_consumed, out_selected);
-}
-static int32_t step_decide_impl(sf_ctx* ctx, int32_t replica, const sf_move_t* edits, const int64_t* offsets, const int32_t* gates, int64_t n,
-                                int32_t group_name_len, int64_t max_moves_per_step, int64_t* out_kept, int64_t* out_n_kept, int64_t* out_scores,
-                                int32_t* out_flags, int64_t* out_consumed, int64_t* out_selected, bool cursor_order);
-// the same step with Move::requires_hard_improvement / requires_score_improvement per candidate (gates[i]: bit 0 / bit 1)
-int32_t sf_step_decide_gated(sf_ctx* ctx, int32_t replica, const sf_move_t* edits, const int64_t* offsets, const int32_t* gates, int64_t n,
-                             int32_t group_name_len, int64_t max_moves_per_step, int64_t* out_kept, int64_t* out_n_kept, int64_t* out_scores,
-                             int32_t* out_flags, int64_t* out_consumed, int64_t* out_selected) {
-    return step_decide_impl(ctx, replica, edits, offsets, gates, n, group_name_len, max_moves_per_step, out_kept, out_n_kept, out_scores, out_flags, out_consumed,
-                            out_selected, false);
-}
-// the step over a cursor's own pull order (RuntimeProviderCursor, runtime/provider_cursor.rs:447-466): no activation is restated here --
-// the cursor has rotated, normalised, deduplicated per provider scope and capped its store, and pushed doable moves only
-// (provider_cursor.rs:420-437) -- so candidate i is pull i; see the header
-int32_t sf_step_decide_cursor(sf_ctx* ctx, int32_t replica, const sf_move_t* edits, const int64_t* offsets, const int32_t* gates, int64_t n,
-                              int64_t* out_scores, int32_t* out_flags, int64_t* out_consumed, int64_t* out_selected) {
-    std::vector<int64_t> kept((size_t)(n > 0 ? n : 1));
-    int64_t nk = 0;
-    return step_decide_impl(ctx, replica, edits, offsets, gates, n, 0, 0, kept.data(), &nk, out_scores, out_flags, out_consumed, out_selected, true);
-}
-static int32_t step_decide_impl(sf_ctx* ctx, int32_t replica, const sf_move_t* edits, const int64_t* offsets, const int32_t* gates, int64_t n,
-                                int32_t group_name_len, int64_t max_moves_per_step, int64_t* out_kept, int64_t* out_n_kept, int64_t* out_scores,
-                                int32_t* out_flags, int64_t* out_consumed, int64_t* out_selected, bool cursor_order) {
-    DeviceGuard _dev(ctx);
-    if (ctx && ctx->xown_level >= 0) return fail(ctx, SF_ERR_UNSUPPORTED, "sf_step_decide_gated: a model with the join of its two planning classes is searched by the fused engine only");
-    if (!ctx || !ctx->initialized || replica < 0 || replica >= ctx->R || n < 0 || !offsets || !out_kept || !out_n_kept || !out_scores || !out_flags ||
-        !out_consumed || !out_selected)
-        return fail(ctx, SF_ERR_INVALID, "bad sf_step_decide arguments");
-    if (!ctx->has_scalar_model || ctx->has_list_model) return fail(ctx, SF_ERR_UNSUPPORTED, "sf_step_decide: scalar-only models (ScalarCandidate edits)");
-    if (ctx->sm.grp_level >= 0 && ctx->sm.grp_mode >= 1)
-        return fail(ctx, SF_ERR_UNSUPPORTED, "compound candidates on a load_balance / balance model (floating-point aggregate) are not chained on the device");
-    if (ctx->sm.run_level >= 0) return fail(ctx, SF_ERR_UNSUPPORTED, "compound candidates on a consecutive-runs model are not chained on the device");
-    if (ctx->cfg.acceptor != SF_ACCEPT_HILL_CLIMBING && ctx->cfg.acceptor != SF_ACCEPT_LATE_ACCEPTANCE && ctx->cfg.acceptor != SF_ACCEPT_DIVERSIFIED_LATE_ACCEPTANCE)
-        return fail(ctx, SF_ERR_UNSUPPORTED, "sf_step_decide: HillClimbing, LateAcceptance or DiversifiedLateAcceptance");
-    if (offsets[0] != 0) return fail(ctx, SF_ERR_INVALID, "offsets[0] must be 0");
-    if (n >= ((int64_t)1 << 31)) return fail(ctx, SF_ERR_UNSUPPORTED, "sf_step_decide: fewer than 2^31 candidates");
-    for (int64_t i = 0; i < n; ++i)
-        if (offsets[i + 1] < offsets[i]) return fail(ctx, SF_ERR_INVALID, "offsets must not decrease");
-    if (n > 0 && offsets[n] > 0 && !edits) return fail(ctx, SF_ERR_INVALID, "edits is NULL");
-    int rc = alloc_search(ctx);
-    if (rc) return rc;
-    SearchParams p = ctx->sp;
-    fill_search_params(ctx, p);
-    const ClassSpec& c = ctx->classes[ctx->scalar_desc];
-    const int ne = ctx->sm.n;
-    // the step's MoveStreamContext and the replica's working values (the cursor filters by is_doable_on)
-    std::vector<int32_t> vals((size_t)ne);
-    uint64_t step_index = 0, draws = 0;
-    HIPCHK(ctx, hipMemcpyAsync(vals.data(), ctx->sm.vals + (size_t)replica * ne, (size_t)ne * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&step_index, p.step_index + replica, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&draws, p.seed_draws + replica, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    uint64_t sseed = step_seed(p.random_seed + (uint64_t)replica, draws);
-    if (ctx->d_explicit && (int64_t)draws < ctx->n_explicit) {
-        HIPCHK(ctx, hipMemcpy(&sseed, ctx->d_explicit + (size_t)replica * ctx->n_explicit + draws, 8, hipMemcpyDeviceToHost));
-    }
-    const StreamCtx sctx{step_index, sseed, p.order};
-    const int64_t cap = max_moves_per_step > 0 ? max_moves_per_step : 256;  // candidate-backed group (grouped_scalar.rs:27-40)
-    // GroupedScalarCursor::activate, Candidates arm (grouped_scalar.rs:122-176)
-    std::vector<int64_t> kept;
-    auto legal = [&](int32_t e, int32_t to) {
-        if (e < 0 || e >= ne) return false;
-        if (to < 0) return to == -1 && c.allows_unassigned != 0;
-        if (to >= c.n_values) return false;
-        if (c.value_off.empty()) return true;
-        for (uint32_t q = c.value_off[(size_t)e]; q < c.value_off[(size_t)e + 1]; ++q)
-            if (c.value_list[q] == to) return true;
-        return false;
-    };
-    for (int64_t o = 0; cursor_order && o < n; ++o) {  // a cursor's store: pull order, nothing skipped; malformed records are the caller's error
-        const int64_t b = offsets[o], e = offsets[o + 1];
-        if (e == b) return fail(ctx, SF_ERR_INVALID, "sf_step_decide_cursor: a candidate without edits (the cursor normalises its store)");
-        if (e - b > SF_COMPOUND_MAX) return fail(ctx, SF_ERR_UNSUPPORTED, "at most 8 edits per compound candidate on the device");
-        for (int64_t k = b; k < e; ++k) {
-            if (edits[k].kind != SF_MOVE_CHANGE) return fail(ctx, SF_ERR_INVALID, "a ScalarEdit is a SF_MOVE_CHANGE-shaped record");
-            for (int64_t j = b; j < k; ++j)
-                if (edits[j].a == edits[k].a) return fail(ctx, SF_ERR_INVALID, "sf_step_decide_cursor: two edits on one entity (the cursor normalises its store)");
-            if (!legal(edits[k].a, edits[k].value)) return fail(ctx, SF_ERR_INVALID, "sf_step_decide_cursor: an edit outside the entity's value range");
-        }
-        kept.push_back(o);
-    }
-    for (int64_t o = 0; !cursor_order && o < n && (int64_t)kept.size() < cap; ++o) {
-        const int64_t idx = (int64_t)sctx.selection_index((uint32_t)o, (uint32_t)n, 0xC0A1E5CEAAA00001ULL ^ (uint64_t)group_name_len);  // apply_selection_order
-        const int64_t b = offsets[idx], e = offsets[idx + 1];
-        if (e == b) continue;
-        if (e - b > SF_COMPOUND_MAX) return fail(ctx, SF_ERR_UNSUPPORTED, "at most 8 edits per compound candidate on the device");
-        bool ok = true, changes = false;
-        for (int64_t k = b; k < e && ok; ++k) {
-            if (edits[k].kind != SF_MOVE_CHANGE) return fail(ctx, SF_ERR_INVALID, "a ScalarEdit is a SF_MOVE_CHANGE-shaped record");
-            for (int64_t j = b; j < k; ++j) ok = ok && edits[j].a != edits[k].a;  // two edits on one (descriptor, entity, variable)
-            ok = ok && legal(edits[k].a, edits[k].value);
-            if (ok) changes = changes || vals[(size_t)edits[k].a] != edits[k].value;
-        }
-        if (!ok || !changes) continue;
-        bool seen = false;
-        for (int64_t q : kept) {
-            if (offsets[q + 1] - offsets[q] != e - b) continue;
-            bool same = true;
-            for (int64_t k = 0; k < e - b && same; ++k) same = edits[offsets[q] + k].a == edits[b + k].a && edits[offsets[q] + k].value == edits[b + k].value;
-            seen = seen || same;
-        }
-        if (seen) continue;
-        kept.push_back(idx);
-    }
-    const int64_t nk = (int64_t)kept.size();
-    *out_n_kept = nk;
-    for (int64_t i = 0; i < nk; ++i) out_kept[i] = kept[(size_t)i];
-    // kept candidates as their own CSR
-    std::vector<sf_move_t> kedits;
-    std::vector<int64_t> koff(1, 0);
-    for (int64_t q : kept) {
-        for (int64_t k = offsets[q]; k < offsets[q + 1]; ++k) kedits.push_back(edits[k]);
-        koff.push_back((int64_t)kedits.size());
-    }
-    int32_t* d_edits = nullptr;
-    int64_t *d_off = nullptr, *d_sc = nullptr, *d_res = nullptr;
-    int32_t *d_do = nullptr, *d_fl = nullptr, *d_gates = nullptr;
-    auto release = [&]() {
-        (void)hipFree(d_edits), (void)hipFree(d_off), (void)hipFree(d_sc), (void)hipFree(d_res), (void)hipFree(d_do), (void)hipFree(d_fl), (void)hipFree(d_gates);
-    };
-    std::vector<int32_t> kgates;  // in pull order
-    if (gates)
-        for (int64_t q : kept) kgates.push_back(gates[q]);
-    const size_t nk1 = (size_t)(nk > 0 ? nk : 1);
-    hipError_t e = hipMalloc((void**)&d_edits, (kedits.empty() ? 1 : kedits.size()) * 24);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_off, (size_t)(nk + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_sc, nk1 * ctx->levels * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_do, nk1 * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_fl, nk1 * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_res, 16);
-    if (e == hipSuccess && !kedits.empty()) e = hipMemcpyAsync(d_edits, kedits.data(), kedits.size() * 24, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_off, koff.data(), (size_t)(nk + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_fl, 0, nk1 * 4, ctx->stream);
-    if (e == hipSuccess && !kgates.empty()) {
-        e = hipMalloc((void**)&d_gates, kgates.size() * 4);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_gates, kgates.data(), kgates.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-    }
-    if (e != hipSuccess) {
-        release();
-        return fail(ctx, SF_ERR_HIP, hipGetErrorString(e));
-    }
-    if (nk > 0)
-        hipLaunchKernelGGL(k_scalar_evaluate_compound, dim3((int)((nk + 255) / 256)), dim3(256), scalar_table_bytes(ctx), ctx->stream, ctx->sm, replica, d_edits,
-                           d_off, nk, d_sc, d_do);
-    hipLaunchKernelGGL(k_scalar_step_decide, dim3(1), dim3(64), scalar_table_bytes(ctx), ctx->stream, ctx->sm, p, replica, d_edits, d_off, nk, d_sc, d_do, d_fl,
-                       d_res, (const int32_t*)d_gates, ctx->hard_levels);
-    e = hipGetLastError();
-    int64_t res[2] = {0, -1};
-    if (e == hipSuccess) e = hipMemcpyAsync(res, d_res, 16, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && nk > 0) e = hipMemcpyAsync(out_scores, d_sc, (size_t)nk * ctx->levels * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && nk > 0) e = hipMemcpyAsync(out_flags, d_fl, (size_t)nk * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    release();
-    if (e != hipSuccess) return fail(ctx, SF_ERR_HIP, hipGetErrorString(e));
-    *out_consumed = res[0];
-    *out_selected = res[1];
-    return SF_OK;
-}
-
-// The join of the two planning classes under sf_apply / sf_apply_compound: its delta is priced on the state BEFORE the move (into ctx->d_xown_delta,
-// SF_MAX_LEVELS words), and added to the committed score by xown_commit once the apply kernel has said the move went through (ctx->d_ok).
-static int xown_price(sf_ctx* ctx, int32_t replica, const sf_move_t* records, int64_t n_records, const int64_t* compound_offsets) {
-    if (ctx->xown_level < 0) return SF_OK;
-    if (!ctx->d_xown_delta) {
-        int rc = dalloc(ctx, &ctx->d_xown_delta, (size_t)SF_MAX_LEVELS);
-        if (rc) return rc;
-    }
-    int32_t* d_rec = nullptr;
-    int64_t* d_off = nullptr;
-    hipError_t e = hipMalloc((void**)&d_rec, (size_t)n_records * 24);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_rec, records, (size_t)n_records * 24, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(ctx->d_xown_delta, 0, (size_t)SF_MAX_LEVELS * 8, ctx->stream);
-    if (e == hipSuccess && compound_offsets) {
-        e = hipMalloc((void**)&d_off, 16);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_off, compound_offsets, 16, hipMemcpyHostToDevice, ctx->stream);
-    }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_cross_owner_holders, dim3(1), dim3(256), 0, ctx->stream, ctx->lm, replica, ctx->sm.n, ctx->d_xown_tab);
-        if (compound_offsets)  // ONE compound candidate: records [0, n_records)
-            hipLaunchKernelGGL(k_cross_owner_evaluate_compound, dim3(1), dim3(256), 0, ctx->stream, ctx->sm.vals, ctx->sm.n, ctx->d_xown_tab, replica, d_rec, d_off,
-                               (int64_t)1, ctx->levels, ctx->xown_level, ctx->xown_weight, ctx->d_xown_delta, (const int32_t*)nullptr);
-        else
-            hipLaunchKernelGGL(k_cross_owner_evaluate_moves, dim3(1), dim3(256), 0, ctx->stream, ctx->lm, ctx->sm.vals, ctx->sm.n, ctx->d_xown_tab, replica, d_rec,
-                               (int64_t)1, ctx->xown_level, ctx->xown_weight, ctx->d_xown_delta, (const int32_t*)nullptr);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (the host buffers are released below)
-    (void)hipFree(d_rec);
-    (void)hipFree(d_off);
-    if (e != hipSuccess) return fail(ctx, SF_ERR_HIP, hipGetErrorString(e));
-    return SF_OK;
-}
-static void xown_commit(sf_ctx* ctx, int32_t replica) {
-    if (ctx->xown_level < 0) return;
-    hipLaunchKernelGGL(k_cross_owner_commit, dim3(1), dim3(1), 0, ctx->stream, ctx->lm.score + (size_t)replica * 4 + ctx->xown_level,
-                       ctx->d_xown_delta + ctx->xown_level, ctx->d_ok);
-}
-
-int32_t sf_apply(sf_ctx* ctx, int32_t replica, const sf_move_t* mv) {
-    DeviceGuard _dev(ctx);
-    if (!ctx || !ctx->initialized || !mv || replica < 0 || replica >= ctx->R)
-        return fail(ctx, SF_ERR_INVALID, "bad sf_apply arguments");
-    if (ctx->xown_level >= 0 && mv->kind == SF_MOVE_LIST_RUIN) return fail(ctx, SF_ERR_UNSUPPORTED, "the join of the two planning classes is not priced by a ruin's recreate");
-    int rc = alloc_search(ctx);
-    if (rc) return rc;
-    if (mv->kind == SF_MOVE_LIST_RUIN) {  // committed ruin + recreate: its own kernel (one wavefront)
-        if (!ctx->has_list_model) return fail(ctx, SF_ERR_INVALID, "list move on a model without a list variable");
-        if (ctx->pm.on) {  // the recreate by the precedence constraint; the committed scores are refreshed from the new lists
-            int32_t* d_mv = nullptr;
-            int64_t* d_sc = nullptr;
-            int32_t* d_do = nullptr;
-            hipError_t e = hipMalloc((void**)&d_mv, 24);
-            if (e == hipSuccess) e = hipMalloc((void**)&d_sc, 4 * 8);
-            if (e == hipSuccess) e = hipMalloc((void**)&d_do, 4);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_mv, mv, 24, hipMemcpyHostToDevice, ctx->stream);
-            int32_t ok = 0;
-            int rc2 = SF_OK;
-            if (e == hipSuccess) rc2 = launch_prec_ruin_moves(ctx, replica, d_mv, std::vector<int32_t>{0}, d_sc, d_do, 1);
-            if (e == hipSuccess && rc2 == SF_OK) e = hipMemcpy(&ok, d_do, 4, hipMemcpyDeviceToHost);
-            (void)hipFree(d_mv);
-            (void)hipFree(d_sc);
-            (void)hipFree(d_do);
-            if (rc2) return rc2;
-            if (e != hipSuccess) return fail(ctx, SF_ERR_HIP, hipGetErrorString(e));
-            if (!ok) return fail(ctx, SF_ERR_INVALID, "move is not doable");
-            return run_evaluate_all(ctx, nullptr, 1);
-        }
-        if (ctx->has_scalar_model) return fail(ctx, SF_ERR_UNSUPPORTED, "sf_apply of a list ruin on a mixed model");
-        if (ctx->lm.n_cap > 65535 || ctx->lm.dim > 65536 || RuinMoveCarve(ctx->lm.V, ctx->lm.n_cap).total > SF_LDS_BUDGET)
-            return fail(ctx, SF_ERR_UNSUPPORTED, "list ruin moves: the list class must fit one wave's LDS slice with 16-bit elements");
-        int32_t* d_mv = nullptr;
-        int64_t* d_sc = nullptr;
-        int32_t* d_do = nullptr;
-        hipError_t e = hipMalloc((void**)&d_mv, 24);
-        if (e == hipSuccess) e = hipMalloc((void**)&d_sc, 4 * 8);
-        if (e == hipSuccess) e = hipMalloc((void**)&d_do, 4);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_mv, mv, 24, hipMemcpyHostToDevice, ctx->stream);
-        int32_t ok = 0;
-        if (e == hipSuccess) e = launch_ruin_moves(ctx, replica, d_mv, std::vector<int32_t>{0}, d_sc, d_do, 1);
-        if (e == hipSuccess) e = hipMemcpy(&ok, d_do, 4, hipMemcpyDeviceToHost);
-        (void)hipFree(d_mv);
-        (void)hipFree(d_sc);
-        (void)hipFree(d_do);
-        if (e != hipSuccess) return fail(ctx, SF_ERR_HIP, hipGetErrorString(e));
-        if (!ok) return fail(ctx, SF_ERR_INVALID, "move is not doable");
-        return SF_OK;
-    }
-    if (mv->kind == SF_MOVE_LIST_MULTI_SWAP) {  // the lists are pairwise different: the swaps commute, so they are committed one after the other
-        if (!ctx->has_list_model) return fail(ctx, SF_ERR_INVALID, "list move on a model without a list variable");
-        if (mv->a < 1 || mv->a > 3) return fail(ctx, SF_ERR_INVALID, "multi-swap: 1..3 swaps");
-        sf_move_t one[3];
-        const int32_t words[3] = {mv->a_pos, mv->b, mv->b_pos};
-        for (int q = 0; q < mv->a; ++q) {
-            const uint32_t w = (uint32_t)words[q];
-            const int32_t dl = (int32_t)(int8_t)(((uint32_t)mv->value >> (8 * q)) & 0xFFu);
-            one[q] = sf_move_t{SF_MOVE_LIST_SWAP, (int32_t)(w & 0xFFFFu), (int32_t)(w >> 16), (int32_t)(w & 0xFFFFu), (int32_t)(w >> 16) + dl, -1};
-            for (int q2 = 0; q2 < q; ++q2)
-                if (one[q2].a == one[q].a) return fail(ctx, SF_ERR_INVALID, "multi-swap: the swaps must touch pairwise different lists");
-            if (dl == 0 || one[q].b_pos < 0) return fail(ctx, SF_ERR_INVALID, "multi-swap: a swap needs two different positions");
-        }
-        for (int q = 0; q < mv->a; ++q) {
-            const int32_t rc2 = sf_apply(ctx, replica, &one[q]);
-            if (rc2 != SF_OK) {
-                for (int q2 = q - 1; q2 >= 0; --q2) (void)sf_apply(ctx, replica, &one[q2]);  // a swap is its own inverse
-                return rc2;
-            }
-        }
-        return SF_OK;
-    }
-    const bool list_move = (mv->kind >= SF_MOVE_LIST_CHANGE && mv->kind <= SF_MOVE_KOPT) || mv->kind == SF_MOVE_LIST_PERMUTE;
-    if (list_move && !ctx->has_list_model) return fail(ctx, SF_ERR_INVALID, "list move on a model without a list variable");
-    if (!list_move && !ctx->has_scalar_model) return fail(ctx, SF_ERR_INVALID, "scalar move on a model without a scalar variable");
-    if (list_move) {
-        if (mv->a < 0 || mv->a >= ctx->lm.V || mv->b < 0 || (mv->kind != SF_MOVE_KOPT && mv->b >= ctx->lm.V) || mv->a_pos < 0 ||
-            mv->b_pos < 0)
-            return fail(ctx, SF_ERR_INVALID, "move out of range");
-        if (mv->kind == SF_MOVE_KOPT && (mv->value < 0 || mv->value >= 7))
-            return fail(ctx, SF_ERR_INVALID, "3-opt move: value is the reconnection pattern 0..6");
-        if (mv->kind == SF_MOVE_LIST_PERMUTE && (mv->a != mv->b || mv->b_pos - mv->a_pos < 2 || mv->b_pos - mv->a_pos > 8 || mv->value < 1))
-            return fail(ctx, SF_ERR_INVALID, "list permute move: a window of 2..8 positions of one list and a permutation rank >= 1");
-        if (mv->kind == SF_MOVE_SUBLIST_CHANGE && (mv->value <= mv->a_pos || mv->value - mv->a_pos > 255))
-            return fail(ctx, SF_ERR_INVALID, "sublist move: value must be the segment end (segment of 1..255 elements)");
-        if (mv->kind == SF_MOVE_SUBLIST_SWAP && (mv->value <= 0 || (mv->value & 0xFFFF) == 0 || (mv->value & 0xFFFF) > 255 ||
-                                                 (mv->value >> 16) == 0 || (mv->value >> 16) > 255))
-            return fail(ctx, SF_ERR_INVALID, "sublist swap: value packs the two segment sizes (1..255 each)");
-        if ((rc = xown_price(ctx, replica, mv, 1, nullptr))) return rc;
-        hipLaunchKernelGGL(k_list_apply, dim3(1), dim3(256), 0, ctx->stream, ctx->lm, replica, mv->kind,
-                           (uint32_t)mv->a, (uint32_t)mv->a_pos, (uint32_t)mv->b, (uint32_t)mv->b_pos,
-                           (uint32_t)(mv->value > 0 ? mv->value : 0), ctx->d_ok);
-        if (ctx->pm.on)  // a move that was not doable left the lists alone: the refresh then changes nothing
-            hipLaunchKernelGGL(k_prec_after_apply, dim3(1), dim3(64), 0, ctx->stream, ctx->lm, ctx->pm, replica);
-    } else {
-        if ((rc = xown_price(ctx, replica, mv, 1, nullptr))) return rc;
-        hipLaunchKernelGGL(k_scalar_apply, dim3(1), dim3(64), scalar_table_bytes(ctx), ctx->stream, ctx->sm, replica, mv->kind, mv->a,
-                           mv->b, mv->value, ctx->d_ok);
-    }
-    xown_commit(ctx, replica);
-    HIPCHK(ctx, hipGetLastError());
-    int32_t ok = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&ok, ctx->d_ok, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (!ok) return fail(ctx, SF_ERR_INVALID, "move is not doable");
-    return SF_OK;
-}
-
-// ≙ ListCheapestInsertionPhase over every replica's current lists (csrc/sf_construct.hip)
-// cheapest insertion on a list class scored by the precedence constraint (k_prec_construct_cheapest); with the slot's precedence policy
-// the phase has the hooks and re-ranks the elements by their downstream chain (cheapest/kernel.rs:75-81,162-229)
-static int ensure_plf(sf_ctx* ctx);
-static int construct_cheapest_precedence(sf_ctx* ctx, const uint32_t* elements, int32_t n, int64_t* out_scores) {
-    if (ctx->lm.dist_level >= 0 || ctx->lm.cap_level >= 0)
-        return fail(ctx, SF_ERR_UNSUPPORTED, "cheapest insertion on a precedence model with distance / capacity constraints");
-    if (int rc = ensure_plf(ctx)) return rc;
-    std::vector<uint32_t> order(elements, elements + n);
-    const PrecSpec& ps = ctx->prec;
-    const size_t nodes = ps.dur.size();
-    if (ctx->prec_policy && n > 0) {  // precedence_downstream: unassigned elements only (those already in a list are skipped by the kernel anyway)
-        std::vector<char> in_list(nodes, 0);
-        {
-            std::vector<uint32_t> off((size_t)ctx->lm.V + 1), vis;
-            if (hipMemcpy(off.data(), ctx->lm.off, off.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, SF_ERR_HIP, "copy of the list offsets");
-            vis.resize(off.back());
-            if (!vis.empty() && hipMemcpy(vis.data(), ctx->lm.visits, vis.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
-                return fail(ctx, SF_ERR_HIP, "copy of the lists");
-            for (uint32_t x : vis)
-                if (x < nodes) in_list[x] = 1;
-        }
-        std::vector<uint32_t> el;
-        for (uint32_t x : order)
-            if (x < nodes && !in_list[x]) el.push_back(x);
-        const size_t m = el.size();
-        std::vector<int64_t> position(nodes, -1);
-        bool ok = true;
-        for (size_t i = 0; i < m; ++i) position[el[i]] = (int64_t)i;
-        std::vector<std::vector<size_t>> succ(m);
-        std::vector<size_t> preds(m, 0);
-        for (size_t i = 0; i < m; ++i)
-            for (uint32_t t = ps.succ_off[el[i]]; t < ps.succ_off[el[i] + 1]; ++t) {
-                const uint32_t to = ps.succ[t];
-                if (to >= nodes || position[to] < 0) continue;
-                succ[i].push_back((size_t)position[to]);
-                preds[(size_t)position[to]] += 1;
-            }
-        std::vector<size_t> ready, topo;
-        for (size_t i = 0; i < m; ++i)
-            if (preds[i] == 0) ready.push_back(i);
-        while (!ready.empty()) {
-            const size_t i = ready.back();
-            ready.pop_back();
-            topo.push_back(i);
-            for (size_t s2 : succ[i])
-                if (--preds[s2] == 0) ready.push_back(s2);
-        }
-        ok = topo.size() == m;
-        if (ok) {
-            std::vector<int64_t> down(m);
-            for (size_t t = m; t-- > 0;) {
-                const size_t i = topo[t];
-                int64_t tail = 0;
-                for (size_t s2 : succ[i]) tail = std::max(tail, down[s2]);
-                down[i] = (int64_t)ps.dur[el[i]] + tail;
-            }
-            std::vector<size_t> idx(m);
-            for (size_t i = 0; i < m; ++i) idx[i] = i;
-            std::stable_sort(idx.begin(), idx.end(), [&](size_t a, size_t b) { return down[a] > down[b]; });
-            order.clear();
-            for (size_t i : idx) order.push_back(el[i]);
-        }
-    }
-    const size_t lds = (((size_t)ctx->lm.V + 1 + 3) & ~(size_t)3) * 4 + ((((size_t)ctx->lm.dim + 31) / 32 + 3) & ~(size_t)3) * 4 + (size_t)ctx->lm.n_cap * 2 + 16;
-    if (lds > SF_LDS_BUDGET) return fail(ctx, SF_ERR_UNSUPPORTED, "list class does not fit one wave's LDS slice");
-    uint32_t* d_el = nullptr;
-    if (!order.empty()) {
-        hipError_t ea = hipMalloc((void**)&d_el, order.size() * 4);
-        if (ea == hipSuccess) ea = hipMemcpyAsync(d_el, order.data(), order.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (ea != hipSuccess) {
-            (void)hipFree(d_el);
-            return fail(ctx, SF_ERR_HIP, hipGetErrorString(ea));
-        }
-    }
-    const int lvl_order = ctx->pm.hard_level < ctx->pm.mk_level ? 0 : (ctx->pm.hard_level > ctx->pm.mk_level ? 1 : 2);
-    auto kern = k_prec_construct_cheapest;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) hipLaunchKernelGGL(kern, dim3(ctx->R), dim3(64), lds, ctx->stream, ctx->lm, ctx->pm, ctx->plf, d_el, (int)order.size(), lvl_order, ctx->sp.stats);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_el);
-    if (e != hipSuccess) return fail(ctx, SF_ERR_HIP, hipGetErrorString(e));
-    return run_evaluate_all(ctx, out_scores, 1);
-}
-
-int32_t sf_construct_list_cheapest(sf_ctx* ctx, int32_t descriptor_index, const uint32_t* elements, int32_t n, int64_t* out_scores) {
-    DeviceGuard _dev(ctx);
-    if (ctx && ctx->xown_level >= 0) return fail(ctx, SF_ERR_UNSUPPORTED, "sf_construct_list_cheapest: a model with the join of its two planning classes is searched by the fused engine only");
-    if (!ctx || !ctx->initialized) return fail(ctx, SF_ERR_INVALID, "sf_initialize first");
-    if (!ctx->has_list_model || descriptor_index != ctx->list_desc) return fail(ctx, SF_ERR_INVALID, "cheapest insertion needs the list variable's class");
-    if (n < 0 || (n > 0 && !elements)) return fail(ctx, SF_ERR_INVALID, "bad sf_construct_list_cheapest arguments");
-    if (ctx->lm.n_cap > 65535 || ctx->lm.dim > 65536) return fail(ctx, SF_ERR_UNSUPPORTED, "construction packs list elements in 16 bits");
-    for (int32_t k = 0; k < n; ++k)
-        if (elements[k] >= (uint32_t)ctx->lm.dim) return fail(ctx, SF_ERR_INVALID, "element id out of range");
-    int rc = alloc_search(ctx);
-    if (rc) return rc;
-    if (ctx->pm.on) return construct_cheapest_precedence(ctx, elements, n, out_scores);
-    const ConstructCarve cv(ctx->lm.V, ctx->lm.n_cap, ctx->lm.dim);
-    if (cv.total > SF_LDS_BUDGET) return fail(ctx, SF_ERR_UNSUPPORTED, "list class does not fit one wave's LDS slice");
-    uint32_t* d_el = nullptr;
-    if (n > 0) {
-        hipError_t ea = hipMalloc((void**)&d_el, (size_t)n * 4);
-        if (ea == hipSuccess) ea = hipMemcpyAsync(d_el, elements, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (ea != hipSuccess) {
-            (void)hipFree(d_el);
-            return fail(ctx, SF_ERR_HIP, hipGetErrorString(ea));
-        }
-    }
-    hipError_t e = hipSuccess;
-    if (ctx->levels <= 2) {
-        auto kern = k_list_construct_cheapest<2>;
-        e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv.total);
-        if (e == hipSuccess) hipLaunchKernelGGL(kern, dim3(ctx->R), dim3(64), cv.total, ctx->stream, ctx->lm, d_el, n, ctx->sp.stats);
-    } else {
-        auto kern = k_list_construct_cheapest<4>;
-        e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv.total);
-        if (e == hipSuccess) hipLaunchKernelGGL(kern, dim3(ctx->R), dim3(64), cv.total, ctx->stream, ctx->lm, d_el, n, ctx->sp.stats);
-    }
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_el);
-    if (e != hipSuccess) return fail(ctx, SF_ERR_HIP, hipGetErrorString(e));
-    return run_evaluate_all(ctx, out_scores, 1);  // finish_construction: the committed score of the constructed lists
-}
-
-// ≙ ListRegretInsertionPhase over every replica's current lists (csrc/sf_construct.hip)
-int32_t sf_construct_list_regret(sf_ctx* ctx, int32_t descriptor_index, const uint32_t* elements, int32_t n, const int64_t* order_keys,
-                                 const int32_t* owners, int64_t* out_scores) {
-    DeviceGuard _dev(ctx);
-    if (ctx && ctx->xown_level >= 0) return fail(ctx, SF_ERR_UNSUPPORTED, "sf_construct_list_regret: a model with the join of its two planning classes is searched by the fused engine only");
-    if (!ctx || !ctx->initialized) return fail(ctx, SF_ERR_INVALID, "sf_initialize first");
-    if (!ctx->has_list_model || descriptor_index != ctx->list_desc) return fail(ctx, SF_ERR_INVALID, "regret insertion needs the list variable's class");
-    if (n < 0 || (n > 0 && !elements)) return fail(ctx, SF_ERR_INVALID, "bad sf_construct_list_regret arguments");
-    if (ctx->lm.n_cap > 65535 || ctx->lm.dim > 65536 || n > 65535) return fail(ctx, SF_ERR_UNSUPPORTED, "construction packs list elements in 16 bits");
-    if (ctx->pm.on) return fail(ctx, SF_ERR_UNSUPPORTED, "regret insertion on a model with precedence hooks");
-    {
-        std::vector<uint8_t> seen((size_t)ctx->lm.dim, 0);
-        for (int32_t k = 0; k < n; ++k) {
-            if (elements[k] >= (uint32_t)ctx->lm.dim) return fail(ctx, SF_ERR_INVALID, "element id out of range");
-            if (seen[elements[k]]++) return fail(ctx, SF_ERR_INVALID, "duplicate element id (the source binding of the phase refuses it, regret.rs:228-236)");
-            if (owners && owners[k] < -1) return fail(ctx, SF_ERR_INVALID, "owners[k]: -1 = unrestricted, otherwise the owner hook's value");
-        }
-    }
-    int rc = alloc_search(ctx);
-    if (rc) return rc;
-    // the unassigned elements in (construction order key, source index) order (execute.rs:81-88); an element whose owner hook names
-    // no list has no candidate entity (mod.rs:104-114) and is never placed: dropped here
-    std::vector<int32_t> order;
-    for (int32_t k = 0; k < n; ++k)
-        if (!owners || owners[k] < ctx->lm.V) order.push_back(k);
-    if (order_keys) std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return order_keys[a] < order_keys[b]; });
-    const int32_t ne = (int32_t)order.size();
-    std::vector<uint32_t> el((size_t)ne);
-    std::vector<int32_t> ow((size_t)ne, -1);
-    std::vector<uint64_t> bucket((size_t)(ctx->lm.V > 0 ? ctx->lm.V : 1), 0);
-    for (int32_t k = 0; k < ne; ++k) {
-        el[k] = elements[order[k]];
-        if (owners) ow[k] = owners[order[k]];
-        if (ow[k] >= 0) bucket[ow[k]] += 1;
-    }
-    if (owners) {  // kernel/fallback.rs:58-84: all-fixed-owner inputs above the trial budget take bounded fallbacks that are not built.  The
-        // budget is checked on the fixed-owner elements handed over (a replica's unassigned subset can only be smaller)
-        uint64_t trials = 0;
-        for (uint64_t len : bucket) trials += len * (len + 1) * (len + 2) / 6;
-        if (trials > 16384) return fail(ctx, SF_ERR_UNSUPPORTED, "owner-restricted regret insertion above the reference's trial budget (regret/kernel/fallback.rs)");
-    }
-    const RegretCarve cv(ctx->lm.V, ctx->lm.n_cap, ctx->lm.dim, ne);
-    if (cv.total > SF_LDS_BUDGET) return fail(ctx, SF_ERR_UNSUPPORTED, "list class does not fit one wave's LDS slice");
-    uint32_t* d_el = nullptr;
-    int32_t* d_ow = nullptr;
-    if (ne > 0) {
-        hipError_t ea = hipMalloc((void**)&d_el, (size_t)ne * 4);
-        if (ea == hipSuccess) ea = hipMalloc((void**)&d_ow, (size_t)ne * 4);
-        if (ea == hipSuccess) ea = hipMemcpy(d_el, el.data(), (size_t)ne * 4, hipMemcpyHostToDevice);
-        if (ea == hipSuccess) ea = hipMemcpy(d_ow, ow.data(), (size_t)ne * 4, hipMemcpyHostToDevice);
-        if (ea != hipSuccess) {
-            (void)hipFree(d_el);
-            (void)hipFree(d_ow);
-            return fail(ctx, SF_ERR_HIP, hipGetErrorString(ea));
-        }
-    }
-    hipError_t e = hipSuccess;
-    if (ctx->levels <= 2) {
-        auto kern = k_list_construct_regret<2>;
-        e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv.total);
-        if (e == hipSuccess) hipLaunchKernelGGL(kern, dim3(ctx->R), dim3(64), cv.total, ctx->stream, ctx->lm, d_el, owners ? d_ow : (const int32_t*)nullptr, ne, ctx->sp.stats);
-    } else {
-        auto kern = k_list_construct_regret<4>;
-        e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv.total);
-        if (e == hipSuccess) hipLaunchKernelGGL(kern, dim3(ctx->R), dim3(64), cv.total, ctx->stream, ctx->lm, d_el, owners ? d_ow : (const int32_t*)nullptr, ne, ctx->sp.stats);
-    }
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_el);
-    (void)hipFree(d_ow);
-    if (e != hipSuccess) return fail(ctx, SF_ERR_HIP, hipGetErrorString(e));
-    return run_evaluate_all(ctx, out_scores, 1);  // the committed score of the constructed lists
-}
-
-// ≙ ListKOptPhase (route-local 2-opt) over every replica's current lists (csrc/sf_clarke_wright.hip)
-int32_t sf_construct_list_k_opt(sf_ctx* ctx, int32_t descriptor_index, int32_t k, int32_t feasible_mode, int32_t max_sweeps, int64_t* out_scores) {
-    DeviceGuard _dev(ctx);
-    if (ctx && ctx->xown_level >= 0) return fail(ctx, SF_ERR_UNSUPPORTED, "sf_construct_list_k_opt: a model with the join of its two planning classes is searched by the fused engine only");
-    if (!ctx || !ctx->initialized) return fail(ctx, SF_ERR_INVALID, "sf_initialize first");
-    if (!ctx->has_list_model || descriptor_index != ctx->list_desc) return fail(ctx, SF_ERR_INVALID, "list k-opt needs the list variable's class");
-    if (feasible_mode < 0 || feasible_mode > 2) return fail(ctx, SF_ERR_INVALID, "feasible_mode: 0 no feasibility hook, 1 capacity, 2 capacity + time windows");
-    if (max_sweeps < 1) return fail(ctx, SF_ERR_INVALID, "max_sweeps must be >= 1 (the termination policy of the phase)");
-    if (ctx->lm.n_cap > 65535 || ctx->lm.dim > 65536) return fail(ctx, SF_ERR_UNSUPPORTED, "construction packs list elements in 16 bits");
-    if (ctx->pm.on) return fail(ctx, SF_ERR_UNSUPPORTED, "list k-opt on a model with precedence hooks");
-    if (!ctx->lm.mat) return fail(ctx, SF_ERR_UNSUPPORTED, "list k-opt needs the distance matrix (route_distance)");
-    if (feasible_mode >= 1 && !ctx->lm.demand) return fail(ctx, SF_ERR_INVALID, "capacity feasibility needs the demand column");
-    if (feasible_mode == 2 && !ctx->tw.uploaded) return fail(ctx, SF_ERR_INVALID, "feasible_mode 2 needs the time windows (sf_list_set_time_windows)");
-    int rc = alloc_search(ctx);
-    if (rc) return rc;
-    if (k == 2 && ctx->lm.V > 0) {  // only k = 2 is implemented by the reference: every other value is a scored no-op (kernel.rs:69-77)
-        const size_t lds = align_up((size_t)ctx->lm.n_cap * 2, 16) + 16;
-        if (lds > SF_LDS_BUDGET) return fail(ctx, SF_ERR_UNSUPPORTED, "a route does not fit one wave's LDS slice");
-        const dim3 grid((unsigned)ctx->lm.V, (unsigned)ctx->R);
-        // the complete hook is a kernel of its own (sf_kopt_tw.hip); modes 0 / 1 launch the instantiation they always did
-        const void* kern = feasible_mode == 2 ? (const void*)k_list_construct_two_opt_tw : (const void*)k_list_construct_two_opt;
-        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess) {
-            if (feasible_mode == 2)
-                hipLaunchKernelGGL(k_list_construct_two_opt_tw, grid, dim3(64), lds, ctx->stream, ctx->lm, tw_tables(ctx), max_sweeps, ctx->sp.stats);
-            else
-                hipLaunchKernelGGL(k_list_construct_two_opt, grid, dim3(64), lds, ctx->stream, ctx->lm, feasible_mode, max_sweeps, ctx->sp.stats);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return fail(ctx, SF_ERR_HIP, hipGetErrorString(e));
-    }
-    return run_evaluate_all(ctx, out_scores, 1);
-}
-
-// ≙ ProblemData{time_windows, service_durations, travel_times, vehicle_departure_time} (solverforge-cvrp problem_data.rs:20-23).  Values are
-// data, never refused: what the reference's recurrence makes of them (infeasible routes) is what the device makes of them.
-int32_t sf_list_set_time_windows(sf_ctx* ctx, int32_t descriptor_index, int32_t n_nodes, const int64_t* lo, const int64_t* hi, const int64_t* service,
-                                 const int64_t* travel, int64_t departure) {
-    DeviceGuard _dev(ctx);
-    if (!ctx) return SF_ERR_INVALID;
-    if (!ctx->classes.count(descriptor_index) || !ctx->classes[descriptor_index].has_list)
-        return fail(ctx, SF_ERR_INVALID, "sf_list_set_time_windows: declare the list variable first");
-    if (!lo || !hi || !service || !travel) return fail(ctx, SF_ERR_INVALID, "sf_list_set_time_windows: null array");
-    const int32_t want = ctx->initialized ? ctx->lm.dim : ctx->classes[descriptor_index].element_bound;
-    if (ctx->initialized ? n_nodes != want : n_nodes < want || n_nodes < 1)
-        return fail(ctx, SF_ERR_INVALID, "sf_list_set_time_windows: n_nodes must equal the list variable's element id bound (the matrix dimension when a matrix is attached)");
-    auto& tw = ctx->tw;
-    const size_t n = (size_t)n_nodes;
-    tw.lo.assign(lo, lo + n), tw.hi.assign(hi, hi + n), tw.service.assign(service, service + n), tw.travel.assign(travel, travel + n * n);
-    tw.departure = departure, tw.n = n_nodes, tw.desc = descriptor_index, tw.set = true;
-    return ctx->initialized ? tw_upload(ctx) : SF_OK;
-}
-
-// ≙ route_hooks::feasible (helpers.rs:109-119) on every replica's committed lists
-int32_t sf_list_routes_feasible(sf_ctx* ctx, int32_t descriptor_index, int32_t feasible_mode, int32_t* out_flags) {
-    DeviceGuard _dev(ctx);
-    if (!ctx || !ctx->initialized) return fail(ctx, SF_ERR_INVALID, "sf_initialize first");
-    if (!ctx->has_list_model || descriptor_index != ctx->list_desc) return fail(ctx, SF_ERR_INVALID, "sf_list_routes_feasible needs the list variable's class");
-    if (!out_flags) return fail(ctx, SF_ERR_INVALID, "sf_list_routes_feasible: null argument");
-    if (feasible_mode != 1 && feasible_mode != 2) return fail(ctx, SF_ERR_INVALID, "feasible_mode: 1 capacity, 2 capacity + time windows");
-    if (!ctx->lm.demand) return fail(ctx, SF_ERR_INVALID, "capacity feasibility needs the demand column");
-    if (feasible_mode == 2 && !ctx->tw.uploaded) return fail(ctx, SF_ERR_INVALID, "feasible_mode 2 needs the time windows (sf_list_set_time_windows)");
-    if (ctx->lm.V == 0) return SF_OK;
-    const size_t n = (size_t)ctx->R * ctx->lm.V;
-    int32_t* d_out = nullptr;
-    hipError_t e = hipMalloc((void**)&d_out, n * 4);
-    if (e != hipSuccess) return fail(ctx, SF_ERR_HIP, hipGetErrorString(e));
-    hipLaunchKernelGGL(k_list_routes_feasible, dim3((unsigned)ctx->lm.V, (unsigned)ctx->R), dim3(64), 0, ctx->stream, ctx->lm, tw_tables(ctx), feasible_mode, d_out);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out_flags, d_out, n * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_out);
-    if (e != hipSuccess) return fail(ctx, SF_ERR_HIP, hipGetErrorString(e));
-    return SF_OK;
-}
-
-// Which evaluation of the time recurrence feasible_mode 2 takes.  A pure query: out_path 0 = no windows set, 1 = the checked lane-serial walk,
-// 2 = the composed wave-wide fold (the host range check of the tables passed and the walk is not forced); out_last_ran = the path the last
-// mode-2 kernel of this context reports having taken (written by the kernel itself), 0 = none has run since the tables were set.
-int32_t sf_list_time_window_path(sf_ctx* ctx, int32_t descriptor_index, int32_t* out_path, int32_t* out_last_ran) {
-    DeviceGuard _dev(ctx);
-    if (!ctx || !ctx->initialized) return fail(ctx, SF_ERR_INVALID, "sf_initialize first");
-    if (!ctx->has_list_model || descriptor_index != ctx->list_desc) return fail(ctx, SF_ERR_INVALID, "sf_list_time_window_path needs the list variable's class");
-    if (out_path) *out_path = !ctx->tw.uploaded ? 0 : (ctx->tw.gate_ok && !ctx->tw.force_walk) ? 2 : 1;
-    if (out_last_ran) {
-        *out_last_ran = 0;
-        if (ctx->tw.uploaded) {
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            HIPCHK(ctx, hipMemcpy(out_last_ran, ctx->tw.d_ran, 4, hipMemcpyDeviceToHost));
-        }
-    }
-    return SF_OK;
-}
-
-// force_walk != 0: feasible_mode 2 takes the checked walk whatever the range check of the tables says; 0: it follows the range check again.
-// (The composed fold cannot be forced: it is exact only on data the check admits.)  For measurements and tests; both paths give the reference's verdict.
-int32_t sf_list_force_time_window_walk(sf_ctx* ctx, int32_t descriptor_index, int32_t force_walk) {
-    if (!ctx || !ctx->initialized) return fail(ctx, SF_ERR_INVALID, "sf_initialize first");
-    if (!ctx->has_list_model || descriptor_index != ctx->list_desc) return fail(ctx, SF_ERR_INVALID, "sf_list_force_time_window_walk needs the list variable's class");
-    ctx->tw.force_walk = force_walk != 0;
-    return SF_OK;
-}
-
-// ≙ ListConstructionPhase (round robin) over every replica's current lists (csrc/sf_construct.hip)
-int32_t sf_construct_list_round_robin(sf_ctx* ctx, int32_t descriptor_index, const uint32_t* elements, int32_t n, const int64_t* order_keys,
-                                      const int32_t* owners, int64_t* out_scores) {
-    DeviceGuard _dev(ctx);
-    if (ctx && ctx->xown_level >= 0) return fail(ctx, SF_ERR_UNSUPPORTED, "sf_construct_list_round_robin: a model with the join of its two planning classes is searched by the fused engine only");
-    if (!ctx || !ctx->initialized) return fail(ctx, SF_ERR_INVALID, "sf_initialize first");
-    if (!ctx->has_list_model || descriptor_index != ctx->list_desc) return fail(ctx, SF_ERR_INVALID, "round robin needs the list variable's class");
-    if (n < 0 || (n > 0 && !elements)) return fail(ctx, SF_ERR_INVALID, "bad sf_construct_list_round_robin arguments");
-    if (ctx->lm.n_cap > 65535 || ctx->lm.dim > 65536 || n > 65535) return fail(ctx, SF_ERR_UNSUPPORTED, "construction packs list elements in 16 bits");
-    std::vector<int32_t> order;
-    {
-        std::vector<bool> seen((size_t)ctx->lm.dim, false);
-        for (int32_t k = 0; k < n; ++k) {
-            if (elements[k] >= (uint32_t)ctx->lm.dim) return fail(ctx, SF_ERR_INVALID, "element id out of range");
-            if (seen[elements[k]]) return fail(ctx, SF_ERR_INVALID, "duplicate element");
-            seen[elements[k]] = true;
-            if (owners && owners[k] < -1) return fail(ctx, SF_ERR_INVALID, "owners[k]: -1 = unrestricted, otherwise the owner hook's value");
-            if (owners && owners[k] >= ctx->lm.V) continue;  // OwnerRestriction::Invalid (list_placement.rs:66-67): skipped
-            order.push_back(k);
-        }
-    }
-    if (order_keys) std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return order_keys[a] < order_keys[b]; });
-    const int ne = (int)order.size();
-    int rc = alloc_search(ctx);
-    if (rc) return rc;
-    if (ne == 0 || ctx->lm.V == 0) return run_evaluate_all(ctx, out_scores, 1);
-    std::vector<uint32_t> el((size_t)ne);
-    std::vector<int32_t> ow((size_t)ne, -1);
-    for (int k = 0; k < ne; ++k) {
-        el[k] = elements[order[k]];
-        if (owners) ow[k] = owners[order[k]];
-    }
-    const RoundRobinCarve cv(ctx->lm.V, ctx->lm.n_cap, ctx->lm.dim, ne);
-    if (cv.total > SF_LDS_BUDGET) return fail(ctx, SF_ERR_UNSUPPORTED, "list class does not fit one wave's LDS slice");
-    uint32_t* d_el = nullptr;
-    int32_t* d_ow = nullptr;
-    hipError_t e = hipMalloc((void**)&d_el, (size_t)ne * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_ow, (size_t)ne * 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_el, el.data(), (size_t)ne * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_ow, ow.data(), (size_t)ne * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_list_construct_round_robin, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv.total);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_list_construct_round_robin, dim3(ctx->R), dim3(64), cv.total, ctx->stream, ctx->lm, d_el, owners ? d_ow : (const int32_t*)nullptr, ne,
-                           ctx->sp.stats);
-        e = hipGetLastError();
-    }
-    hipError_t es = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = es;
-    (void)hipFree(d_el), (void)hipFree(d_ow);
-    if (e != hipSuccess) return fail(ctx, SF_ERR_HIP, hipGetErrorString(e));
-    return run_evaluate_all(ctx, out_scores, 1);
-}
-
-// ≙ ListClarkeWrightPhase over every replica's current lists with the stock CVRP hook bundle (csrc/sf_clarke_wright.hip)
-int32_t sf_construct_list_clarke_wright(sf_ctx* ctx, int32_t descriptor_index, const uint32_t* elements, int32_t n, int32_t feasible_mode,
-                                        int64_t* out_scores, int32_t* out_committed) {
-    DeviceGuard _dev(ctx);
-    if (ctx && ctx->xown_level >= 0) return fail(ctx, SF_ERR_UNSUPPORTED, "sf_construct_list_clarke_wright: a model with the join of its two planning classes is searched by the fused engine only");
-    if (!ctx || !ctx->initialized) return fail(ctx, SF_ERR_INVALID, "sf_initialize first");
-    if (!ctx->has_list_model || descriptor_index != ctx->list_desc) return fail(ctx, SF_ERR_INVALID, "Clarke-Wright needs the list variable's class");
-    if (n < 0 || (n > 0 && !elements)) return fail(ctx, SF_ERR_INVALID, "bad sf_construct_list_clarke_wright arguments");
-    if (feasible_mode != 0 && feasible_mode != 1) return fail(ctx, SF_ERR_INVALID, "feasible_mode: 0 structural, 1 capacity");
-    if (ctx->lm.n_cap > 65535 || ctx->lm.dim > 65536) return fail(ctx, SF_ERR_UNSUPPORTED, "construction packs list elements in 16 bits");
-    if (ctx->pm.on) return fail(ctx, SF_ERR_UNSUPPORTED, "Clarke-Wright on a model with precedence hooks");
-    if (!ctx->lm.mat) return fail(ctx, SF_ERR_UNSUPPORTED, "Clarke-Wright needs the distance matrix (savings_distance)");
-    if (feasible_mode == 1 && !ctx->lm.demand) return fail(ctx, SF_ERR_INVALID, "capacity feasibility needs the demand column");
-    // declared elements in source order; a duplicate source key is a binding error in the reference (runtime_list_source.rs);
-    // elements whose value is the depot of the available owners are not routed (kernel.rs:83-91)
-    std::vector<uint32_t> el;
-    {
-        std::vector<bool> seen((size_t)ctx->lm.dim, false);
-        for (int32_t k = 0; k < n; ++k) {
-            if (elements[k] >= (uint32_t)ctx->lm.dim) return fail(ctx, SF_ERR_INVALID, "element id out of range");
-            if (seen[elements[k]]) return fail(ctx, SF_ERR_INVALID, "duplicate element");
-            seen[elements[k]] = true;
-            if ((int32_t)elements[k] != ctx->lm.depot) el.push_back(elements[k]);
-        }
-    }
-    const int ne = (int)el.size();
-    if (ne > 65535) return fail(ctx, SF_ERR_UNSUPPORTED, "Clarke-Wright: more than 65535 elements");
-    int rc = alloc_search(ctx);
-    if (rc) return rc;
-    if (out_committed) std::fill(out_committed, out_committed + ctx->R, 0);
-    if (ne == 0) return run_evaluate_all(ctx, out_scores, 1);
-    const CwCarve cv(ctx->lm.V, ctx->lm.n_cap, ctx->lm.dim, ne);
-    if (cv.total > SF_LDS_BUDGET) return fail(ctx, SF_ERR_UNSUPPORTED, "route state does not fit one wave's LDS slice");
-    int monotone = 1;
-    if (ctx->lm.demand) {
-        std::vector<int32_t> dem((size_t)ctx->lm.dim);
-        hipError_t ed = hipMemcpy(dem.data(), ctx->lm.demand, dem.size() * 4, hipMemcpyDeviceToHost);
-        if (ed != hipSuccess) return fail(ctx, SF_ERR_HIP, hipGetErrorString(ed));
-        for (uint32_t x : el)
-            if (dem[x] < 0) monotone = 0;
-    }
-    if (feasible_mode == 0) monotone = 1;  // no load test: every rejection is permanent
-    const uint64_t P = (uint64_t)ne * (uint64_t)(ne - 1) / 2;
-    uint32_t *d_el = nullptr, *d_v0 = nullptr, *d_v1 = nullptr;
-    int64_t *d_k0 = nullptr, *d_k1 = nullptr;
-    int32_t* d_flag = nullptr;
-    void* d_tmp = nullptr;
-    size_t tmp_bytes = 0;
-    hipError_t e = hipMalloc((void**)&d_el, (size_t)ne * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_flag, (size_t)ctx->R * 4);
-    if (e == hipSuccess && P > 0) e = hipMalloc((void**)&d_k0, P * 8);
-    if (e == hipSuccess && P > 0) e = hipMalloc((void**)&d_k1, P * 8);
-    if (e == hipSuccess && P > 0) e = hipMalloc((void**)&d_v0, P * 4);
-    if (e == hipSuccess && P > 0) e = hipMalloc((void**)&d_v1, P * 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_el, el.data(), (size_t)ne * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && P > 0) {
-        hipLaunchKernelGGL(k_cw_savings, dim3((unsigned)((ne + 255) / 256), (unsigned)ne), dim3(256), 0, ctx->stream, ctx->lm, d_el, ne, d_k0, d_v0);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = rocprim::radix_sort_pairs_desc(nullptr, tmp_bytes, d_k0, d_k1, d_v0, d_v1, (size_t)P, 0, 64, ctx->stream);
-        if (e == hipSuccess) e = hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 16);
-        if (e == hipSuccess) e = rocprim::radix_sort_pairs_desc(d_tmp, tmp_bytes, d_k0, d_k1, d_v0, d_v1, (size_t)P, 0, 64, ctx->stream);
-    }
-    if (e == hipSuccess) {
-        e = hipFuncSetAttribute((const void*)k_cw_merge, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv.total);
-        if (e == hipSuccess)
-            hipLaunchKernelGGL(k_cw_merge, dim3(ctx->R), dim3(64), cv.total, ctx->stream, ctx->lm, d_el, ne, d_v1, P, feasible_mode, monotone, d_flag,
-                               (uint64_t*)nullptr);
-        if (e == hipSuccess) e = hipGetLastError();
-    }
-    if (e == hipSuccess && out_committed) e = hipMemcpyAsync(out_committed, d_flag, (size_t)ctx->R * 4, hipMemcpyDeviceToHost, ctx->stream);
-    hipError_t es = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = es;
-    (void)hipFree(d_el), (void)hipFree(d_flag), (void)hipFree(d_k0), (void)hipFree(d_k1), (void)hipFree(d_v0), (void)hipFree(d_v1), (void)hipFree(d_tmp);
-    if (e != hipSuccess) return fail(ctx, SF_ERR_HIP, hipGetErrorString(e));
-    return run_evaluate_all(ctx, out_scores, 1);  // the committed score of the constructed lists
-}
-
 // ---- search ------------------------------------------------------------------------------
 int32_t sf_solver_configure(sf_ctx* ctx, const sf_solver_config* cfg) {
     if (!ctx || !cfg) return SF_ERR_INVALID;
@@ -2875,6 +1916,8 @@ static int ensure_plf(sf_ctx* ctx) {
     pl.on = 1;
     return SF_OK;
 }
+// the `order` argument of the precedence kernels a host drives: 0 = the penalty's level comes first, 1 = the makespan's, 2 = one level
+static int prec_level_order(const sf_ctx* ctx) { return ctx->pm.hard_level < ctx->pm.mk_level ? 0 : (ctx->pm.hard_level > ctx->pm.mk_level ? 1 : 2); }
 static int launch_mixed(sf_ctx* ctx, SearchParams& p, int grid, bool trace) {
     GLeaves gl{};
     gl.list_desc = ctx->has_list_model ? ctx->list_desc : 0;
@@ -3321,16 +2364,12 @@ int32_t sf_portfolio_migrate_local(sf_ctx* ctx, int32_t n_elite, int32_t n_repla
         adopted += 1;
     }
     if (adopted) {
-        int32_t* d_src = nullptr;
-        hipError_t e = hipMalloc((void**)&d_src, (size_t)ctx->R * 4);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_src, src.data(), (size_t)ctx->R * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_list_migrate, dim3(ctx->R), dim3(256), 0, ctx->stream, ctx->lm, ctx->sp, d_src);
-            e = hipGetLastError();
-        }
+        Scratch<int32_t> d_src;
+        if (int rc = d_src.upload(ctx, src.data(), (size_t)ctx->R)) return rc;
+        hipLaunchKernelGGL(k_list_migrate, dim3(ctx->R), dim3(256), 0, ctx->stream, ctx->lm, ctx->sp, d_src.p);
+        hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        (void)hipFree(d_src);
-        if (e != hipSuccess) return fail(ctx, SF_ERR_HIP, hipGetErrorString(e));
+        if (int rc = hip_rc(ctx, e)) return rc;
     }
     if (out_adopted) *out_adopted = adopted;
     return SF_OK;
@@ -3381,5 +2420,7 @@ extern "C" int32_t sf_debug_phases(uint64_t* out8) {  // diagnostic builds only 
 #endif
 
 #include "sf_api_scalar.inc"
+#include "sf_api_moves.inc"
+#include "sf_api_construct.inc"
 #include "sf_portfolio.inc"
 #include "sf_candidate_trace.inc"

@@ -95,12 +95,17 @@ hipError_t launch_tu_list_block<2>(bool trace, const SearchLaunch& a);
 template <>
 hipError_t launch_tu_list_block<4>(bool trace, const SearchLaunch& a);
 
+// one launch of a kernel that takes dynamic LDS: the attribute of this instantiation, the launch, hipGetLastError()
+template <class K, class... Args>
+inline hipError_t launch_with_lds(K kern, dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args) {
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, grid, block, lds, stream, args...);
+    return hipGetLastError();
+}
 template <class K, class... Args>
 inline hipError_t launch_with_lds(K kern, const SearchLaunch& a, Args... args) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(a.grid), dim3(a.block), a.lds, a.stream, args...);
-    return hipGetLastError();
+    return launch_with_lds(kern, dim3(a.grid), dim3(a.block), a.lds, a.stream, args...);
 }
 
 }  // namespace sf
