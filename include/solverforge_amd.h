@@ -737,7 +737,17 @@ typedef enum sf_generic_launch_bits {
     SF_GEN_NODE_GLOBAL = 2,  /* the node -> slot table in HBM */
     SF_GEN_RING32 = 4,       /* the 32-bit pre-evaluated delta ring */
     SF_GEN_RUIN_SHIFT = 4,   /* bits 4-5: ruin recreate, 0 none / 1 general (matrix gathers) / 2 16-bit leg tables / 3 list-preserving (v2) */
-    SF_GEN_VT_SHIFT = 8      /* bits 8-11: bytes of the scalar value type */
+    SF_GEN_VT_SHIFT = 8,     /* bits 8-11: bytes of the scalar value type */
+    /* placement of a precedence (ListPrecedenceMakespanConstraint) model's launch; bits 12-23 are 0 when SF_GEN_PREC is */
+    SF_GEN_PREC = 1 << 12,           /* a PREC instantiation of the kernel */
+    SF_GEN_PREC_LDS = 1 << 13,       /* the Kahn scratch (12 bytes per node) in the replica's LDS slice (else HBM) */
+    SF_GEN_PREC_STATIC_SHIFT = 14,   /* bits 14-15: workgroup-shared LDS copy of the static graph, 0 none / 1 full / 2 slim */
+    SF_GEN_PREC_GROUPS_SHIFT = 16,   /* bits 16-20: trials per wavefront of the grouped evaluator, 0 (off) / 2 / 4 / 8 / 16 */
+    SF_GEN_PREC_OCC = 1 << 21,       /* MODE 2: the build for four workgroups per CU */
+    SF_GEN_PREC_SWEEP = 1 << 22,     /* HBM scratch: the lane-per-trial sweep of the list change / swap trials */
+    SF_GEN_PREC_INC = 1 << 23,       /* HBM scratch: the incremental trial refresh */
+    SF_GEN_RUIN_INST = 1 << 24,      /* a RUIN instantiation (the union has a list ruin leaf) */
+    SF_GEN_LEVELS_SHIFT = 25         /* bits 25-27: the score-level count the kernel is instantiated for (2 or 4) */
 } sf_generic_launch_bits;
 int32_t sf_list_arith_flags(sf_ctx* ctx, int32_t* out_model, int32_t* out_last_generic);
 /* explicit step seeds for parity runs (n_steps per replica, replica-major); NULL clears */

@@ -1775,7 +1775,9 @@ int32_t sf_phase_start(sf_ctx* ctx) {
 
 // generic N-leaf engine: mixed models, and list models whose union has plain list change / swap leaves
 template <int L, class VT, bool RUIN = false, bool PREC = false>
-static int launch_mixed_t(sf_ctx* ctx, const SearchParams& p, const GLeaves& gl, int n_replicas, bool trace) {
+static int launch_mixed_t(sf_ctx* ctx, const SearchParams& p, const GLeaves& gl_chosen, int n_replicas, bool trace) {
+    GLeaves gl2 = gl_chosen;  // the launch's copy: the fit check below, the delta ring and the node table adjust it
+    const GLeaves& gl = gl2;
     const int ns = ctx->has_scalar_model ? ctx->sm.n : 0;
     const bool tables = ctx->has_scalar_model && ctx->sm.tables();
     // FAST instantiation: the reference's default list policy on a list-only model (see k_mixed_search_wave)
@@ -1793,12 +1795,30 @@ static int launch_mixed_t(sf_ctx* ctx, const SearchParams& p, const GLeaves& gl,
                       (!RUIN || (ctx->lm.leg16 && ctx->lm.V <= 128 && ctx->lm.n_cap <= 32767 && ctx->lm.dim <= 32767 && ctx->lm.small32 && ctx->lm.mat16));
     // (FAST + ruin: the list-preserving recreate only and the node -> slot table in HBM, see the kernel)
     const bool nodeg = fast && (RUIN || SF_MIXED_FAST_NODEG != 0);
-    GCarve<VT> cv(ns, ctx->has_list_model ? ctx->lm.V : 0, ctx->has_list_model ? ctx->lm.n_cap : 0, gl.has_nearby ? ctx->lm.dim : 0,
-                  gl.kopt_nearby, gl.n, gl.has_ruin ? (nodeg ? 3 : (ctx->lm.leg16 ? 2 : 1)) : 0, ctx->has_list_model ? ctx->lm.dim : 0,
-                  PREC && gl.prec_lds ? gl.prec.n : 0, tables ? ctx->sm.n_values : 0, tables && ctx->sm.run_level >= 0 ? ctx->sm.run_P : 0,
-                  PREC && gl.prec_lds ? gl.prec_groups : 0, nodeg);
+    auto carve = [&]() {
+        return GCarve<VT>(ns, ctx->has_list_model ? ctx->lm.V : 0, ctx->has_list_model ? ctx->lm.n_cap : 0, gl.has_nearby ? ctx->lm.dim : 0,
+                          gl.kopt_nearby, gl.n, gl.has_ruin ? (nodeg ? 3 : (ctx->lm.leg16 ? 2 : 1)) : 0, ctx->has_list_model ? ctx->lm.dim : 0,
+                          PREC && gl.prec_lds ? gl.prec.n : 0, tables ? ctx->sm.n_values : 0, tables && ctx->sm.run_level >= 0 ? ctx->sm.run_P : 0,
+                          PREC && gl.prec_lds ? gl.prec_groups : 0, nodeg);
+    };
+    GCarve<VT> cv = carve();
+    // launch_mixed sized the shared static copy against a slice WITHOUT the grouped evaluator's scratch (it picks the groups afterwards):
+    // when the real slice with the copy beside it fails launch_mixed's own fit rule, the groups are halved until it passes -- without them
+    // the slice is at most the one the estimate passed, so the copy stays -- instead of refusing the launch; should the slice still not
+    // fit, the copy goes too and the graph is read from HBM.  (The rule's 1,024 bytes below SF_LDS_BUDGET matter: the PREC kernels hold
+    // SF_MIXED_PREC_STATIC_LDS bytes of static LDS, so a sum up to the full 160 KiB is a launch the runtime rejects)
+    if (PREC && gl2.prec_static) {
+        auto over = [&]() { return cv.total + 1024 + (size_t)gl2.prec_static > SF_LDS_BUDGET; };
+        while (over() && gl2.prec_groups) {
+            gl2.prec_groups = gl2.prec_groups > 2 ? gl2.prec_groups / 2 : 0;
+            cv = carve();
+        }
+        if (over()) {
+            gl2.prec_static = 0, gl2.prec_static_slim = 0;
+            cv = carve();
+        }
+    }
     if (cv.total > SF_LDS_BUDGET) return fail(ctx, SF_ERR_UNSUPPORTED, "model does not fit one wave's LDS slice");
-    GLeaves gl2 = gl;
     gl2.ringd = nullptr;
     static const bool no_pre_eval = std::getenv("SF_AMD_MIXED_NO_PRE_EVAL") != nullptr;  // diagnostics / parity tests: score inside the replay as before
     if (fast && ctx->lm.small32 && !no_pre_eval && !SF_MIXED_RING_LDS) {  // the scoring stage stores 32-bit deltas
@@ -1834,7 +1854,8 @@ static int launch_mixed_t(sf_ctx* ctx, const SearchParams& p, const GLeaves& gl,
     const char* wenv = std::getenv("SF_AMD_MIXED_WPB");  // diagnostics: cap the replicas per workgroup (A/B of the workgroup shape)
     const int wmax = wenv && std::atoi(wenv) >= 1 && std::atoi(wenv) < 4 ? std::atoi(wenv) : 4;
     for (int w = 1; w <= wmax; ++w) {
-        const size_t per_wg = cv.total * w + (fast ? 0 : 1024) + (PREC ? (size_t)gl.prec_static : 0);  // + the static annealing state (the FAST kernels have none), the shared copy of the precedence graph
+        // + the kernel's static LDS (annealing state 1,024 bytes + the precedence paths' broadcast words; the FAST kernels have none), the shared copy of the precedence graph
+        const size_t per_wg = cv.total * w + (fast ? 0 : (PREC ? SF_MIXED_PREC_STATIC_LDS : SF_MIXED_STATIC_LDS)) + (PREC ? (size_t)gl.prec_static : 0);
         if (per_wg > 160 * 1024) break;
         size_t groups = (160 * 1024) / per_wg;
         if (groups * w > max_waves) groups = max_waves / w;
@@ -1859,7 +1880,13 @@ static int launch_mixed_t(sf_ctx* ctx, const SearchParams& p, const GLeaves& gl,
         const bool v2_ok = lm.V <= 128 && lm.n_cap <= 32767 && lm.dim <= 32767 && lm.small32 && lm.mat16;  // rv2_model_ok
         const int ruin_variant = !gl.has_ruin ? 0 : fast ? 3 : !lm.leg16 ? 1 : v2_ok ? 3 : 2;
         ctx->last_generic_flags = (fast ? SF_GEN_FAST : 0) | (nodeg ? SF_GEN_NODE_GLOBAL : 0) | (gl2.ringd ? SF_GEN_RING32 : 0) |
-                                  (ruin_variant << SF_GEN_RUIN_SHIFT) | ((int32_t)sizeof(VT) << SF_GEN_VT_SHIFT);
+                                  (ruin_variant << SF_GEN_RUIN_SHIFT) | ((int32_t)sizeof(VT) << SF_GEN_VT_SHIFT) |
+                                  (RUIN ? SF_GEN_RUIN_INST : 0) | (L << SF_GEN_LEVELS_SHIFT);
+        if (PREC)  // where the precedence constraint's scratch, static graph and trial evaluation went (what the kernel is handed in gl2)
+            ctx->last_generic_flags |= SF_GEN_PREC | (gl.prec_lds ? SF_GEN_PREC_LDS : 0) |
+                                       ((gl.prec_static ? (gl.prec_static_slim ? 2 : 1) : 0) << SF_GEN_PREC_STATIC_SHIFT) |
+                                       ((gl.prec_lds ? gl.prec_groups : 0) << SF_GEN_PREC_GROUPS_SHIFT) | (prec_occ ? SF_GEN_PREC_OCC : 0) |
+                                       (gl.prec_sweep ? SF_GEN_PREC_SWEEP : 0) | (gl.prec_inc ? SF_GEN_PREC_INC : 0);
     }
     SearchParams q = p;
     q.n_launch = n_replicas;
@@ -2033,7 +2060,7 @@ static int launch_mixed(sf_ctx* ctx, SearchParams& p, int grid, bool trace) {
     // replica's value array in one byte per entity: job shop 500 x 20 fits 4 waves per CU instead of 3)
     gl.levels = ctx->levels;
     gl.prec = ctx->has_list_model ? ctx->pm : PrecModel{};
-    {  // the Kahn scratch (16 bytes per node) goes to LDS while at least 4 replicas still fit a CU
+    {  // the Kahn scratch (12 bytes per node: prec_lds_scratch_bytes) goes to LDS while at least 4 replicas still fit a CU (up to 36 KiB = 3,072 nodes)
         const bool no_lds = std::getenv("SF_AMD_PREC_HBM") != nullptr;  // diagnostics / parity tests: force the HBM scratch (read at every launch)
         // ... and beyond that whenever ONE replica per CU still fits: 10,000 nodes (job shop 500 x 20) run 1.7 x the rate of the HBM scratch with
         // half the replicas (profiles/r05_prec_eval_ab.txt).  SF_AMD_PREC_LDS_MAX_KB caps the scratch (36 = the round-4 rule)

@@ -129,7 +129,7 @@ struct GCarve {
     // entity-order tables), else 0
     // n_leaves rings only: the LDS slice decides how many replicas a CU holds
     // has_ruin: 0 no ruin leaf, 1 general path (slot prefix only), 2 LDS fast path (+ edge table, list-end edges, matrix row; sf_ruin.h)
-    // prec_words: node count of the precedence constraint when its four scratch arrays live in LDS (sf_precedence.h), else 0
+    // prec_words: node count of the precedence constraint when its four scratch arrays live in LDS (12 bytes per node: prec_lds_scratch_bytes), else 0
     // n_table / run_P: per-value tables of the scalar class's value-keyed constraints (n_values entries; the consecutive-runs /
     // presence table behind the count table, as SCarve lays them out), 0 when the class has none
     // has_ruin 3: the list-preserving recreate only (sf_ruin_v2.h; the FAST instantiation): edge table + list-end edges + arena, no matrix row
@@ -325,8 +325,15 @@ namespace sf {
 // MODE 2 (PREC instantiations, untraced): the same code built for four 4-wave workgroups per CU (128 registers per lane).  A precedence
 // trial is one replica's serial chain of Kahn rounds, so a CU that can hold more than eight small replicas (LDS slice permitting) hides
 // that latency with more of them: nine-leaf policy on a 20 x 10 job shop 38.3 M moves/s at 2,048 replicas -> 54.7 M at 4,096, 10 x 5
-// 102.7 M (profiles/r03w_prec_occupancy.txt).  LDS-bound sizes (50 x 20: eight replicas per CU either way) keep MODE 0: -4 % with the
-// smaller register budget.  The host picks per launch (launch_mixed_t).
+// 102.7 M (profiles/r03w_prec_occupancy.txt).  The host picks per launch (launch_mixed_t): untraced, no grouped evaluator, more than 2,048
+// replicas and a slice of at most 17,948 bytes (nine or more replicas per CU).  Since the scratch shrank to 12 bytes per node the 50 x 20
+// shop under the nine-leaf policy is inside that (16,080-byte slice, ten per CU): sf_list_arith_flags reports MODE 2 for it from 2,049
+// replicas on (tests/test_gpu_prec_placement.py); a general graph of 1,218 nodes on eight lists (17,952 bytes) is the first that keeps MODE 0.
+// Static LDS of one workgroup, which the host's workgroup-shape loop adds to the dynamic slices (launch_mixed_t; read back from the code
+// objects' group_segment_fixed_size): the annealing state s_sa, and in the PREC instantiations the broadcast words s_psw_info, s_prec_info
+// and s_plf_info (the others drop them unused).  The FAST kernels have none.  A new __shared__ array belongs in these sums.
+constexpr size_t SF_MIXED_STATIC_LDS = 4 * SA_WORDS * sizeof(uint64_t);
+constexpr size_t SF_MIXED_PREC_STATIC_LDS = SF_MIXED_STATIC_LDS + 64 + 32 + 64;
 #ifndef SF_MIXED_PREC_BLOCKS_PER_CU
 #define SF_MIXED_PREC_BLOCKS_PER_CU 4
 #endif
@@ -354,6 +361,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
     if (rr >= p.n_launch) return;  // no workgroup barrier below
     const int r = rr + p.replica_base;
     __shared__ uint64_t s_sa[FAST ? 1 : 4][FAST ? 1 : SA_WORDS];  // SimulatedAnnealing acceptor state of the resident replicas (FAST: LateAcceptance, no static LDS)
+    static_assert(FAST || sizeof(s_sa) == SF_MIXED_STATIC_LDS, "SF_MIXED_STATIC_LDS counts s_sa");
     uint64_t* saw = s_sa[FAST ? 0 : wave_in_group];
     const bool annealing = acceptor == 3;
     if (annealing) sa_load(saw, p.sa, r, lane);
@@ -550,6 +558,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
         }
         if (prec_sweep) {  // committed evaluation + what the lane-per-trial sweep reads: list predecessors, order positions, round starts, prefix maxima
             __shared__ uint32_t s_psw_info[4][4];
+            static_assert(sizeof(s_psw_info) == 64, "SF_MIXED_PREC_STATIC_LDS counts 64 bytes");
             uint32_t* info = s_psw_info[wave_in_group];
             const PrecResult pr = prec_eval<uint16_t, PrecMemGlobal>(precm, s_visits, s_off, V, prec_E, prec_D, prec_Q, prec_S, psw_lp, info, psw_roff);
             wave_sync();
@@ -629,6 +638,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
         if (!prec_incremental) return prec_eval<uint16_t, PrecMemGlobal>(precm, s_visits, s_off, V, prec_E, prec_D, prec_Q, prec_S);
         // committed evaluation: also the list predecessors, the owner violations, the cycle flag and the makespan multiplicity
         __shared__ uint32_t s_prec_info[4][2];
+        static_assert(sizeof(s_prec_info) == 32, "SF_MIXED_PREC_STATIC_LDS counts 32 bytes");
         uint32_t* info = s_prec_info[wave_in_group];
         const PrecResult pr = prec_eval<uint16_t, PrecMemGlobal>(precm, s_visits, s_off, V, prec_E, prec_D, prec_Q, prec_S, pinc.LP, info);
         wave_sync();
@@ -699,6 +709,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
     bool plf_cur_cyclic = false;                           // the working lists of this step are cyclic
     PlfRep plf{};
     __shared__ uint32_t s_plf_info[4][4];
+    static_assert(sizeof(s_plf_info) == 64, "SF_MIXED_PREC_STATIC_LDS counts 64 bytes");
     uint32_t* const plf_info = s_plf_info[wave_in_group];
     int64_t* const plf_score = plf_on ? gl.plf.score + (size_t)r * GRC * 4 : nullptr;
     int64_t* const plf_cache = plf_on ? gl.plf.cache + (size_t)r * GL * GRC * 2 : nullptr;  // the filter's evaluation per ring slot

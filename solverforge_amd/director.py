@@ -108,6 +108,14 @@ class SolverConfig:
                    random_seed=s.random_seed)
 
 
+def decode_generic_launch_bits(g):
+    """sf_generic_launch_bits (include/solverforge_amd.h) of one generic-engine launch as a dict: see GpuScoreDirector.arith_flags."""
+    return {"fast": bool(g & 1), "node_global": bool(g & 2), "ring32": bool(g & 4), "ruin": (g >> 4) & 3, "value_bytes": (g >> 8) & 15,
+            "prec": bool(g >> 12 & 1), "prec_lds": bool(g >> 13 & 1), "prec_static": (g >> 14) & 3, "prec_groups": (g >> 16) & 31,
+            "prec_occ": bool(g >> 21 & 1), "prec_sweep": bool(g >> 22 & 1), "prec_inc": bool(g >> 23 & 1), "ruin_inst": bool(g >> 24 & 1),
+            "levels": (g >> 25) & 7}
+
+
 class GpuScoreDirector:
     """One device context = `n_replicas` independent Director + search states of one problem."""
 
@@ -607,16 +615,18 @@ class GpuScoreDirector:
     def arith_flags(self):
         """Narrow-arithmetic paths (sf_list_arith_flags): the list model's {"mat32", "mat16", "leg16", "small32",
         "scalar_value_bytes" (of the last scalar-engine launch, 0 = none)} and what the last generic-engine launch took --
-        {"fast", "node_global", "ring32", "ruin" (0 none / 1 general / 2 leg16 / 3 v2), "value_bytes"}, or None before the
+        {"fast", "node_global", "ring32", "ruin" (0 none / 1 general / 2 leg16 / 3 v2), "value_bytes", "ruin_inst", "levels" (the
+        score-level count the kernel was instantiated for: 2 or 4) and the placement of a precedence model's launch: "prec" (a PREC
+        instantiation), "prec_lds" (Kahn scratch in the replica's LDS slice), "prec_static" (0 none / 1 full / 2 slim shared copy of the
+        static graph), "prec_groups" (trials per wavefront of the grouped evaluator, 0 = off), "prec_occ" (MODE 2: the build for four
+        workgroups per CU), "prec_sweep" / "prec_inc" (HBM scratch: lane-per-trial sweep / incremental refresh)}, or None before the
         first one.  Diagnostics for tests."""
         m, g = C.c_int32(0), C.c_int32(0)
         check(self._L.sf_list_arith_flags(self._h, C.byref(m), C.byref(g)), self._h)
         model = {"mat32": bool(m.value & 1), "mat16": bool(m.value & 2), "leg16": bool(m.value & 4), "small32": bool(m.value & 8),
                  "scalar_value_bytes": (m.value >> 8) & 15}
         g = g.value
-        gen = None if g < 0 else {"fast": bool(g & 1), "node_global": bool(g & 2), "ring32": bool(g & 4), "ruin": (g >> 4) & 3,
-                                  "value_bytes": (g >> 8) & 15}
-        return model, gen
+        return model, (None if g < 0 else decode_generic_launch_bits(g))
 
     def best_scores(self):
         return self._scores(self._L.sf_get_best_scores)

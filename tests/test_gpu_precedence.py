@@ -34,6 +34,33 @@ def scratch_mode(request, monkeypatch):
 LEAF_BITS = {"list_change": 4, "list_swap": 8, "list_reverse": 64, "sublist_change": 128, "sublist_swap": 256, "kopt": 512}
 
 
+def _assert_placement(d, mode, n, E, V, owner=True, lds_cap_kb=None, slim=True, whole_slice_fits=None, **over):
+    """The last fused launch went where the scratch_mode parameter says (sf_list_arith_flags; the host's rules in launch_mixed, restated in
+    prec_placement_rules): n nodes, E fixed edges, V lists.  lds: scratch in LDS and the grouped evaluator at the default rule's T;
+    lds_one_trial: T = 0; lds_groups16: the forced T after the 40 KiB halving; lds_static_hbm: no static copy, so T = 0; hbm: the sweep;
+    hbm_full: neither sweep nor incremental refresh; hbm_incremental: the refresh.  Above 3,072 nodes (36 KiB of scratch) the whole-slice
+    rule decides, which depends on the kernel's LDS carve: the caller states its outcome.  (None of these tests has the critical-path
+    leaf, whose tables switch sweep and refresh off.)"""
+    import prec_placement_rules as rules
+
+    lds = not mode.startswith("hbm") and (lds_cap_kb is None or 12 * n <= lds_cap_kb * 1024)
+    if lds and 12 * n > 36 * 1024:
+        assert whole_slice_fits is not None
+        lds = whole_slice_fits
+    static = rules.static_copy(n, E, owner, slim) if lds and mode != "lds_static_hbm" else 0
+    T = rules.trials(n, V, static, forced={"lds_one_trial": 0, "lds_groups16": 16}.get(mode))
+    want = {"prec": True, "prec_lds": lds, "prec_static": static, "prec_groups": T, "prec_sweep": not lds and mode not in ("hbm_full", "hbm_incremental"),
+            "prec_inc": mode == "hbm_incremental", "prec_occ": False, "ruin_inst": False}
+    want.update(over)
+    gen = d.arith_flags()[1]
+    assert gen is not None and {k: gen[k] for k in want} == want, (mode, gen, want)
+
+
+def _shape(p):
+    n = len(p["durations"])
+    return n, sum(1 for s in p["successors"] for t in s if t < n), len(p["sequences"])
+
+
 def _t(moves):
     return np.stack([moves["kind"], moves["a"], moves["a_pos"], moves["b"], moves["b_pos"], moves["value"]], axis=1)
 
@@ -102,7 +129,7 @@ def test_full_scores_and_evaluate_each(oracle, jobs, machines, seed, drop, owner
     assert d.calculate_score()[0][0] == 0 and d.calculate_score()[0][1] < 0  # the step-major schedule is feasible
 
 
-def test_fan_out_graph_beyond_the_node_record(oracle):
+def test_fan_out_graph_beyond_the_node_record(oracle, scratch_mode):
     """A general precedence graph: one hub with 260 fixed successors (the Kahn rounds' node record holds the first successor and an
     out-degree that saturates at 255; the rest come from the CSR), nodes with two and three successors, a chain; most nodes in no
     list.  Full score and the trial score of every list move kind == oracle, in every scratch mode of the fixture."""
@@ -128,6 +155,7 @@ def test_fan_out_graph_beyond_the_node_record(oracle):
         assert len(gm) == len(om) > 0 and (_t(gm) == _t(om)).all()
         os_, od = o.evaluate_moves(om)
         assert (gd == od).all() and (gs == os_[:, :2]).all()
+        _assert_placement(d, scratch_mode, *_shape(p))
     # a short fused search from the acyclic plan keeps replica 0 on the oracle
     p = {"durations": dur, "successors": succ, "expected_owner": owner, "sequences": [[0, 3, 261, 10, 264, 265, 40], [7, 262, 5, 263, 266, 100], [2, 267, 268, 200, 1, 271]]}
     d, o, bits = _mk(oracle, p, leaves=("list_change", "list_swap", "list_reverse"))
@@ -138,13 +166,14 @@ def test_fan_out_graph_beyond_the_node_record(oracle):
     d.phase_start()
     o.phase_start()
     d.solve_steps(25)
+    _assert_placement(d, scratch_mode, *_shape(p))
     o.steps(25)
     assert d.working_lists(0, 0) == o.get_lists(0)
     assert (d.calculate_score()[0] == o.score()[:2]).all()
 
 
 @pytest.mark.parametrize("state", ["scheduled", "shuffled"])
-def test_trial_scores_every_list_move_kind(oracle, state):
+def test_trial_scores_every_list_move_kind(oracle, scratch_mode, state):
     from solverforge_amd import datasets
 
     p = datasets.make_precedence_shop(7, 4, seed=5)
@@ -162,13 +191,14 @@ def test_trial_scores_every_list_move_kind(oracle, state):
         assert (_t(gm) == _t(om)).all()
         os_, od = o.evaluate_moves(om)
         assert (gd == od).all() and (gs == os_[:, :2]).all()
+        _assert_placement(d, scratch_mode, *_shape(p))  # (the cursor is a traced fused launch)
         es, ed = d.evaluate_moves(om)  # sf_step_evaluate on host-provided records
         assert (ed == od).all() and (es == os_[:, :2]).all()
     kinds = set(int(k) for k in _t(gm)[:, 0])
     assert kinds == {2, 3, 4, 5, 6, 7}
 
 
-def test_apply_traced_and_fused_steps(oracle):
+def test_apply_traced_and_fused_steps(oracle, scratch_mode):
     import solverforge_amd as sfa
     from solverforge_amd import datasets
 
@@ -200,7 +230,9 @@ def test_apply_traced_and_fused_steps(oracle):
         if gap:
             assert tuple(gmv) == tuple(omv), step
         assert d.working_lists(0, 0) == o.get_lists(0), step
+    _assert_placement(d, scratch_mode, *_shape(p))
     d.solve_steps(60)
+    _assert_placement(d, scratch_mode, *_shape(p))
     o.steps(60)
     assert d.working_lists(0, 0) == o.get_lists(0)
     assert (d.calculate_score()[0] == o.score()[:2]).all()
@@ -210,12 +242,16 @@ def test_apply_traced_and_fused_steps(oracle):
         assert gst[k] == ost[k], k
 
 
-@pytest.mark.parametrize("jobs,machines,setting", [(30, 20, "default"), (30, 20, "static_in_hbm"), (30, 20, "lds_cap_36"), (3, 70, "default"), (40, 70, "default")])
-def test_larger_shops_setup_paths(oracle, monkeypatch, jobs, machines, setting):
+@pytest.mark.parametrize("jobs,machines,setting", [(30, 20, "default"), (30, 20, "static_in_hbm"), (30, 20, "lds_cap_36"), (3, 70, "default"), (40, 70, "default"),
+                                                   (45, 70, "default")])
+def test_larger_shops_setup_paths(oracle, monkeypatch, scratch_mode, jobs, machines, setting):
     """Round 5: the wave-wide evaluation's set-up walks the lists chunk by chunk with the list offsets held one per lane (fewer than 64 lists) or
     read from the lists' offset table (70 lists here), keeps 16-bit queue / successor arrays in LDS, and reads node records, fixed in-degrees and
     owners from a slim workgroup-shared LDS copy when the full static copy does not fit (600 nodes and more; SF_AMD_PREC_STATIC_SLIM=0 leaves
-    them in HBM).  2,800 nodes (40 x 70) put the scratch beyond the round-4 LDS limit: it stays in LDS as long as one replica per CU fits.
+    them in HBM).  The Kahn scratch is 12 bytes per node: 600 nodes (7,200 bytes) stay in LDS under SF_AMD_PREC_LDS_MAX_KB=36 too, 2,800
+    nodes (40 x 70: 33,600 bytes, slim copy 44,816 bytes: none) are still under the 36 KiB rule, and 3,150 nodes (45 x 70: 37,800 bytes) pass
+    the whole-slice rule -- the scratch stays in LDS because one replica's slice with it still fits a CU.  3 x 70 (210 nodes) has the full
+    copy and, with 70 lists, no grouped evaluator.  Every case asserts its placement; the HBM parameters of the fixture move the scratch.
     Full scores of scheduled / shuffled / partly assigned states, then fused steps == oracle."""
     import solverforge_amd as sfa
     from solverforge_amd import datasets
@@ -238,6 +274,9 @@ def test_larger_shops_setup_paths(oracle, monkeypatch, jobs, machines, setting):
     o.phase_start()
     steps = 4 if jobs * machines > 2000 else 10
     d.solve_steps(steps)
+    # (45 x 70: one replica's slice with the 37,800 bytes of scratch is 45,728 bytes, + 1,024 under the 162,816 of a CU)
+    _assert_placement(d, scratch_mode, *_shape(p0), lds_cap_kb=36 if setting == "lds_cap_36" else None, slim=setting != "static_in_hbm",
+                      whole_slice_fits=True if jobs * machines > 3072 else None)
     o.steps(steps)
     assert d.working_lists(0, 0) == o.get_lists(0)
     assert (d.calculate_score()[0] == o.score()[:2]).all()
@@ -247,7 +286,7 @@ def test_larger_shops_setup_paths(oracle, monkeypatch, jobs, machines, setting):
         assert gst[k] == ost[k], k
 
 
-def test_multi_replica_search_leaves_the_cycle_and_improves(oracle):
+def test_multi_replica_search_leaves_the_cycle_and_improves(oracle, scratch_mode):
     """8 replicas, distinct seeds: every replica == its own oracle run; starting cyclic (hard = -n), the search reaches a feasible
     schedule and a shorter makespan than the step-major start."""
     import solverforge_amd as sfa
@@ -261,6 +300,7 @@ def test_multi_replica_search_leaves_the_cycle_and_improves(oracle):
     d.configure(sfa.SolverConfig(random_seed=100, late_acceptance_size=20, accepted_count_limit=32))
     d.phase_start()
     d.solve_steps(150)
+    _assert_placement(d, scratch_mode, *_shape(p))
     got = d.calculate_score()
     best = d.best_scores()
     for r in (0, 3, 7):
@@ -275,7 +315,7 @@ def test_multi_replica_search_leaves_the_cycle_and_improves(oracle):
     assert best[:, 0].max() == 0
 
 
-def test_three_levels_and_validation(oracle):
+def test_three_levels_and_validation(oracle, scratch_mode):
     import solverforge_amd as sfa
     from solverforge_amd import datasets
 
@@ -287,6 +327,7 @@ def test_three_levels_and_validation(oracle):
     d.phase_start()
     o.phase_start()
     d.solve_steps(30)
+    _assert_placement(d, scratch_mode, *_shape(p), levels=4)
     o.steps(30)
     assert d.working_lists(0, 0) == o.get_lists(0)
     assert (d.calculate_score()[0] == o.score()[:3]).all()
@@ -304,7 +345,7 @@ def test_three_levels_and_validation(oracle):
         d2.calculate_score()
 
 
-def test_mixed_jobshop_with_makespan(oracle):
+def test_mixed_jobshop_with_makespan(oracle, scratch_mode):
     """The mixed job shop (scalar machine_idx + machine sequences, BendableScore<2,1>) with the makespan objective added: list and
     scalar leaves in one union, the precedence constraint on the list class of a two-class model."""
     import solverforge_amd as sfa
@@ -343,7 +384,10 @@ def test_mixed_jobshop_with_makespan(oracle):
         if gap:
             assert tuple(gmv) == tuple(omv), step
             kinds.add(int(gmv["kind"]))
+    shape = (p["n_ops"], int((p["job"][1:] == p["job"][:-1]).sum()), p["n_machines"])
+    _assert_placement(d, scratch_mode, *shape, owner=False, levels=4, value_bytes=2)
     d.solve_steps(80)
+    _assert_placement(d, scratch_mode, *shape, owner=False, levels=4, value_bytes=2)
     o.steps(80)
     assert d.working_lists(1, 0) == o.get_lists(1)
     assert (d.working_values(0, 0) == o.get_vars(0, 0)).all()

@@ -40,6 +40,27 @@ def scratch(request):
         os.environ.pop(k, None)
 
 
+def _assert_placement(d, mode, p, tables=True, owner=True, **over):
+    """The last fused launch went where the `scratch` parameter says (sf_list_arith_flags; the host's rules in launch_mixed, restated in
+    prec_placement_rules).  lds (and the two parameters that only change the leaf's own code paths): scratch in LDS, the grouped evaluator
+    at the default rule's T; lds_one_trial: T = 0; lds_groups2 / lds_groups16: the forced T after the 40 KiB halving; hbm: scratch in
+    HBM -- with the sweep, unless the launch carries the critical-path leaf's per-replica tables (the leaf, the slot's policy or a ruin
+    leaf: `tables`), which re-evaluate in the main scratch arrays.  Up to 3,072 nodes (36 KiB of scratch) here."""
+    import prec_placement_rules as rules
+
+    n, V = len(p["durations"]), len(p["sequences"])
+    E = sum(1 for s in p["successors"] for t in s if t < n)
+    assert 12 * n <= 36 * 1024
+    lds = mode != "hbm"
+    static = rules.static_copy(n, E, owner) if lds else 0
+    T = rules.trials(n, V, static, forced={"lds_one_trial": 0, "lds_groups2": 2, "lds_groups16": 16}.get(mode))
+    want = {"prec": True, "prec_lds": lds, "prec_static": static, "prec_groups": T, "prec_sweep": not lds and not tables, "prec_inc": False,
+            "prec_occ": False, "levels": 2, "value_bytes": 2}
+    want.update(over)
+    gen = d.arith_flags()[1]
+    assert gen is not None and {k: gen[k] for k in want} == want, (mode, gen, want)
+
+
 def _pair(oracle, p, leaves, seed, n_replicas=1, la=5, limit=25, with_owner=True):
     import solverforge_amd as sfa
 
@@ -75,6 +96,7 @@ def test_streams_with_trial_scores(oracle, scratch, jobs, machines, seed, leaves
             os_, od = o.evaluate_moves(om)
             assert (gd == od).all() and (gs == os_[:, :2]).all(), (order, si)
             seen |= set(int(k) for k in _t(gm)[:, 0])
+            _assert_placement(d, scratch, p, ruin_inst=False)  # (the cursor is a traced fused launch)
             es, ed = d.evaluate_moves(om)  # sf_step_evaluate on host-provided records: every kind, multi-swaps and ruins with hooks included
             assert (ed == od).all() and (es == os_[:, :2]).all(), (order, si)
     assert {2, 3, 4, 8} <= seen  # change, swap, reverse, ruin at least
@@ -160,8 +182,10 @@ def test_traced_and_fused_steps(oracle, scratch):
                 assert tuple(gmv) == tuple(omv), step
                 kinds.add(int(gmv["kind"]))
             assert d.working_lists(0, 0) == o.get_lists(0), step
+        _assert_placement(d, scratch, p, ruin_inst=False)
         d.solve_steps(10)
         d.solve_steps(10)
+        _assert_placement(d, scratch, p, ruin_inst=False)
         scores = d.calculate_score()
         for r in range(R):
             o = mk(11 + r)
@@ -287,6 +311,7 @@ def test_route_graph_filter_streams(oracle, scratch, leaves):
             assert (_t(gm) == _t(om)).all(), (policy, order)
             os_, od = o.evaluate_moves(om)
             assert (gd == od).all() and (gs == os_[:, :2]).all(), (policy, order)
+            _assert_placement(d, scratch, p, tables=policy or "precedence" in leaves, ruin_inst=False)
         if policy:
             n_policy = len(gm)
         else:
@@ -315,7 +340,9 @@ def test_policy_steps_from_acyclic_and_cyclic_starts(oracle, scratch):
             assert gap == oap
             if gap:
                 assert tuple(gmv) == tuple(omv), step
+        _assert_placement(d, scratch, p, ruin_inst=True)
         d.solve_steps(12)
+        _assert_placement(d, scratch, p, ruin_inst=True)
         scores = d.calculate_score()
         for r in range(R):
             o = mk(21 + r)
@@ -540,16 +567,21 @@ def test_precedence_ruin_rolls_back_when_nothing_is_safe(oracle):
     assert (ed == hd).all() and (es == hs[:, :2]).all()
 
 
-def test_high_occupancy_instantiation(oracle):
-    """Launches with more than eight replicas per CU take the PREC kernels built for four workgroups per CU (MODE 2): same results."""
+def test_high_occupancy_instantiation(oracle, monkeypatch):
+    """Launches with more than 2,048 replicas whose LDS slice lets more than eight share a CU take the PREC kernels built for four
+    workgroups per CU (MODE 2; here the PREC + RUIN one): same results.  MODE 2 is not taken with the grouped evaluator, which the default
+    rule switches on for a 15-node shop -- as written before that condition existed this test ran MODE 0 -- so the evaluator is off here
+    (SF_AMD_PREC_GROUPS is read at every launch); tests/test_gpu_prec_placement.py reaches MODE 2 under default settings on larger shops."""
     from solverforge_amd import datasets
 
+    monkeypatch.setenv("SF_AMD_PREC_GROUPS", "0")
     p = datasets.make_precedence_shop(5, 3, seed=4)
     R = 2304
     d, mk = _policy_pair(oracle, p, POLICY_LEAVES, 40, n_replicas=R, ruin=(2, 4, 3))
     d.calculate_score()
     d.phase_start()
     d.solve_steps(6)
+    _assert_placement(d, "lds_one_trial", p, prec_occ=True, ruin_inst=True)
     scores = d.calculate_score()
     for r in (0, 1, 777, R - 1):
         o = mk(40 + r)
@@ -629,7 +661,9 @@ def test_nine_leaf_policy_under_the_default_forager(oracle, scratch, limit, cycl
             assert tuple(gmv) == tuple(omv), step
         gated += int(((gf >> 4) & 1).sum())
         improving += int(len(gm) > 0 and (gf[-1] & 6) == 6)  # the step ended on an accepted candidate that is the pick
+    _assert_placement(d, scratch, p, ruin_inst=True)
     d.solve_steps(15)
+    _assert_placement(d, scratch, p, ruin_inst=True)
     scores = d.calculate_score()
     for r in range(R):
         o = mk(51 + r)
@@ -717,7 +751,8 @@ def test_element_capacity_below_the_node_count(oracle):
 
 
 def test_critical_path_leaf_beyond_2048_nodes(oracle):
-    """Round 4 lifted the leaf's 2,048-node limit (64-bit multi-swap stream).  A 60 x 40 shop (2,400 nodes: Kahn scratch in HBM): traced
+    """Round 4 lifted the leaf's 2,048-node limit (64-bit multi-swap stream).  A 60 x 40 shop (2,400 nodes: 28,800 bytes of Kahn scratch, in LDS since
+    the scratch shrank to 12 bytes per node; slim static copy of 38,416 bytes, no grouped evaluator -- asserted): traced
     steps of the leaf beside change + swap == oracle, then fused steps with the counters.  (At this size the stream still fits 32 bits --
     the 64-bit plumbing is what the index64 parametrisation of the other tests runs; the reference's own cursor counts its triples with
     three nested loops, so no oracle run exists where the count passes 2^32.)"""
@@ -738,7 +773,9 @@ def test_critical_path_leaf_beyond_2048_nodes(oracle):
         assert gap == oap
         if gap:
             assert tuple(gmv) == tuple(omv), step
+    _assert_placement(d, "lds", p, ruin_inst=False)
     d.solve_steps(2)
+    _assert_placement(d, "lds", p, ruin_inst=False)
     o.steps(2)
     assert (d.calculate_score()[0] == o.score()[:2]).all() and d.working_lists(0, 0) == o.get_lists(0)
     gst, ost = d.stats(0), o.stats()
