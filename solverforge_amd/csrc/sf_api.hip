@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1774,124 +1775,37 @@ int32_t sf_phase_start(sf_ctx* ctx) {
 }  // extern "C"
 
 // generic N-leaf engine: mixed models, and list models whose union has plain list change / swap leaves
-template <int L, class VT, bool RUIN = false, bool PREC = false>
-static int launch_mixed_t(sf_ctx* ctx, const SearchParams& p, const GLeaves& gl_chosen, int n_replicas, bool trace) {
-    GLeaves gl2 = gl_chosen;  // the launch's copy: the fit check below, the delta ring and the node table adjust it
-    const GLeaves& gl = gl2;
-    const int ns = ctx->has_scalar_model ? ctx->sm.n : 0;
-    const bool tables = ctx->has_scalar_model && ctx->sm.tables();
-    // FAST instantiation: the reference's default list policy on a list-only model (see k_mixed_search_wave)
-    static const bool no_fast = std::getenv("SF_AMD_MIXED_NO_FAST") != nullptr;  // diagnostics / parity tests: force the general instantiation
-    bool fast_kinds = true;  // the leaf kinds the FAST instantiation keeps (the default list policy of a slot with a distance meter)
-    for (int l = 0; l < gl.n; ++l) {
-        const int k = gl.kind[l];
-        fast_kinds = fast_kinds && (k == 16 || k == 32 || k == 64 || k == 128 || k == 256 || k == 1024 || (k == 512 && gl.kopt_nearby));
+#include "sf_mixed_plan.h"  // GenericShape / GenericKnobs / plan_generic_launch: every decision about the launch, made once
+
+// what plan_generic_launch reads of the context, the launch's parameters and the union's leaves
+static GenericShape generic_shape(const sf_ctx* ctx, const SearchParams& p, const GLeaves& gl, int n_replicas, bool trace) {
+    GenericShape s{};
+    const ScalarModel& sm = ctx->sm;
+    const ListModel& lm = ctx->lm;
+    s.has_list = ctx->has_list_model, s.has_scalar = ctx->has_scalar_model;
+    if (s.has_scalar) s.n_scalar = sm.n, s.n_values = sm.n_values, s.tables = sm.tables(), s.run_level = sm.run_level, s.run_P = sm.run_P;
+    if (s.has_list)
+        s.V = lm.V, s.n_cap = lm.n_cap, s.dim = lm.dim, s.leg16 = lm.leg16 != 0, s.small32 = lm.small32 != 0, s.mat16 = lm.mat16 != 0,
+        s.mat_symmetric = lm.mat_symmetric != 0, s.dist_level = lm.dist_level;
+    s.levels = ctx->levels, s.n_leaves = gl.n;
+    for (int l = 0; l < gl.n; ++l) s.kind[l] = gl.kind[l];
+    s.has_nearby = gl.has_nearby, s.kopt_nearby = gl.kopt_nearby, s.has_ruin = gl.has_ruin, s.union_custom = gl.union_custom, s.union_order = gl.union_order;
+    s.acceptor = p.acceptor, s.forager = p.forager, s.order = p.order, s.dry_run = p.dry_run, s.legacy_eval = p.legacy_eval, s.explicit_seeds = p.explicit_seeds != nullptr;
+    s.prec_on = gl.prec.on, s.prec_n = gl.prec.n, s.prec_edges = gl.prec.n_edges, s.prec_owner = gl.prec.owner != nullptr, s.plf_on = gl.plf.on;
+    s.n_replicas = n_replicas, s.trace = trace;
+    return s;
+}
+// the plan's four numbers -> the 12 specialisations of launch_tu_mixed (csrc/Makefile: MIXED)
+static hipError_t dispatch_tu_mixed(const GenericPlan& pl, bool trace, const SearchLaunch& a) {
+    switch (pl.levels * 1000 + pl.value_bytes * 100 + pl.ruin_inst * 10 + pl.prec) {
+#define SF_MIXED_CASE(L, VTB, RUIN, PREC) \
+    case L * 1000 + VTB * 100 + RUIN * 10 + PREC: return launch_tu_mixed<L, VTB, RUIN != 0, PREC != 0>(trace, pl.mode, a);
+        SF_MIXED_CASE(2, 2, 0, 0) SF_MIXED_CASE(4, 2, 0, 0) SF_MIXED_CASE(2, 1, 0, 0) SF_MIXED_CASE(4, 1, 0, 0)
+        SF_MIXED_CASE(2, 2, 1, 0) SF_MIXED_CASE(4, 2, 1, 0) SF_MIXED_CASE(2, 2, 0, 1) SF_MIXED_CASE(4, 2, 0, 1)
+        SF_MIXED_CASE(2, 1, 0, 1) SF_MIXED_CASE(4, 1, 0, 1) SF_MIXED_CASE(2, 2, 1, 1) SF_MIXED_CASE(4, 2, 1, 1)
+#undef SF_MIXED_CASE
     }
-    const bool fast = !no_fast && !trace && !PREC && sizeof(VT) == 2 && ctx->has_list_model && !ctx->has_scalar_model && p.acceptor == SF_ACCEPT_LATE_ACCEPTANCE &&
-                      p.forager == SF_FORAGER_ACCEPTED_COUNT && !p.dry_run && !gl.union_custom && gl.union_order == SF_UNION_STRATIFIED_RANDOM && gl.n > 1 &&
-                      (ctx->lm.mat_symmetric || ctx->lm.dist_level < 0) && !p.legacy_eval && !p.explicit_seeds && fast_kinds &&
-                      p.order == SF_ORDER_RANDOM &&  // (the default policy's SelectionOrder: compiled in, see StreamCtx in the kernel)
-                      // with a ruin leaf the FAST kernel carries the list-preserving recreate only (sf_ruin_v2.h: rv2_model_ok + the edge table)
-                      (!RUIN || (ctx->lm.leg16 && ctx->lm.V <= 128 && ctx->lm.n_cap <= 32767 && ctx->lm.dim <= 32767 && ctx->lm.small32 && ctx->lm.mat16));
-    // (FAST + ruin: the list-preserving recreate only and the node -> slot table in HBM, see the kernel)
-    const bool nodeg = fast && (RUIN || SF_MIXED_FAST_NODEG != 0);
-    auto carve = [&]() {
-        return GCarve<VT>(ns, ctx->has_list_model ? ctx->lm.V : 0, ctx->has_list_model ? ctx->lm.n_cap : 0, gl.has_nearby ? ctx->lm.dim : 0,
-                          gl.kopt_nearby, gl.n, gl.has_ruin ? (nodeg ? 3 : (ctx->lm.leg16 ? 2 : 1)) : 0, ctx->has_list_model ? ctx->lm.dim : 0,
-                          PREC && gl.prec_lds ? gl.prec.n : 0, tables ? ctx->sm.n_values : 0, tables && ctx->sm.run_level >= 0 ? ctx->sm.run_P : 0,
-                          PREC && gl.prec_lds ? gl.prec_groups : 0, nodeg);
-    };
-    GCarve<VT> cv = carve();
-    // launch_mixed sized the shared static copy against a slice WITHOUT the grouped evaluator's scratch (it picks the groups afterwards):
-    // when the real slice with the copy beside it fails launch_mixed's own fit rule, the groups are halved until it passes -- without them
-    // the slice is at most the one the estimate passed, so the copy stays -- instead of refusing the launch; should the slice still not
-    // fit, the copy goes too and the graph is read from HBM.  (The rule's 1,024 bytes below SF_LDS_BUDGET matter: the PREC kernels hold
-    // SF_MIXED_PREC_STATIC_LDS bytes of static LDS, so a sum up to the full 160 KiB is a launch the runtime rejects)
-    if (PREC && gl2.prec_static) {
-        auto over = [&]() { return cv.total + 1024 + (size_t)gl2.prec_static > SF_LDS_BUDGET; };
-        while (over() && gl2.prec_groups) {
-            gl2.prec_groups = gl2.prec_groups > 2 ? gl2.prec_groups / 2 : 0;
-            cv = carve();
-        }
-        if (over()) {
-            gl2.prec_static = 0, gl2.prec_static_slim = 0;
-            cv = carve();
-        }
-    }
-    if (cv.total > SF_LDS_BUDGET) return fail(ctx, SF_ERR_UNSUPPORTED, "model does not fit one wave's LDS slice");
-    gl2.ringd = nullptr;
-    static const bool no_pre_eval = std::getenv("SF_AMD_MIXED_NO_PRE_EVAL") != nullptr;  // diagnostics / parity tests: score inside the replay as before
-    if (fast && ctx->lm.small32 && !no_pre_eval && !SF_MIXED_RING_LDS) {  // the scoring stage stores 32-bit deltas
-        if (!ctx->d_mixed_ringd) {
-            int32_t* rd = nullptr;
-            int rc = dalloc(ctx, &rd, (size_t)ctx->R * GL * GRC * 2);
-            if (rc) return rc;
-            ctx->d_mixed_ringd = rd;
-        }
-        gl2.ringd = ctx->d_mixed_ringd;
-    }
-    if (nodeg) {
-        if (!ctx->d_node_tab32) {
-            uint32_t* nt = nullptr;
-            int rc = dalloc(ctx, &nt, (size_t)ctx->R * ctx->lm.dim);
-            if (rc) return rc;
-            ctx->d_node_tab32 = nt;
-        }
-        gl2.node_tab = ctx->d_node_tab32;
-    }
-    // replicas (waves) per workgroup: the count that keeps the most waves resident per CU (a workgroup's LDS is
-    // allocated as a whole; the kernel is built for SF_MIXED_BLOCKS_PER_CU workgroups of 4 waves per CU, the FAST
-    // instantiation for SF_MIXED_FAST_BLOCKS_PER_CU); ties go to the larger group
-    // precedence models: the four-workgroups-per-CU build when the launch has more replicas than two workgroups per CU hold and the LDS
-    // slice lets more than eight share a CU (sf_mixed_wave.hip: MODE 2)
-    static const bool no_prec_occ = std::getenv("SF_AMD_PREC_NO_OCC") != nullptr;
-    // (not with the grouped evaluator: its scratch leaves room for 8 - 10 replicas per CU, and the 128-register build is slower per wave:
-    // nine-leaf policy 20 x 10 at 6,144 replicas 71 M moves/s with it, 106 M without)
-    const bool prec_occ = PREC && !trace && !no_prec_occ && !gl.prec_groups && n_replicas > 8 * 256 && (160 * 1024) / (cv.total + 256) > 8;
-    const size_t max_waves = 4 * (size_t)(fast ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_PER_CU : SF_MIXED_FAST_BLOCKS_PER_CU) : (prec_occ ? SF_MIXED_PREC_BLOCKS_PER_CU : SF_MIXED_BLOCKS_PER_CU));  // by register budget
-    int wpb = 1;
-    size_t best_resident = 0;
-    const char* wenv = std::getenv("SF_AMD_MIXED_WPB");  // diagnostics: cap the replicas per workgroup (A/B of the workgroup shape)
-    const int wmax = wenv && std::atoi(wenv) >= 1 && std::atoi(wenv) < 4 ? std::atoi(wenv) : 4;
-    for (int w = 1; w <= wmax; ++w) {
-        // + the kernel's static LDS (annealing state 1,024 bytes + the precedence paths' broadcast words; the FAST kernels have none), the shared copy of the precedence graph
-        const size_t per_wg = cv.total * w + (fast ? 0 : (PREC ? SF_MIXED_PREC_STATIC_LDS : SF_MIXED_STATIC_LDS)) + (PREC ? (size_t)gl.prec_static : 0);
-        if (per_wg > 160 * 1024) break;
-        size_t groups = (160 * 1024) / per_wg;
-        if (groups * w > max_waves) groups = max_waves / w;
-        if (groups * w >= best_resident) {
-            best_resident = groups * w;
-            wpb = w;
-        }
-    }
-    if (best_resident == 0) return fail(ctx, SF_ERR_UNSUPPORTED, "generic engine: one replica's LDS slice (with the precedence scratch / static copy) exceeds a CU's 160 KiB");
-    static const bool dbg_launch = std::getenv("SF_AMD_DEBUG_LAUNCH") != nullptr;  // diagnostics: the launch shape, once per change
-    if (dbg_launch) {
-        static size_t last = 0;
-        const size_t key = cv.total * 131 + (size_t)wpb * 7 + (size_t)n_replicas + (prec_occ ? 1 : 0);
-        if (key != last) {
-            last = key;
-            std::fprintf(stderr, "[sf] generic engine launch: L=%d ruin=%d prec=%d fast=%d prec_occ=%d replicas=%d LDS/replica=%zu B (prec groups %d, static %d B) waves/workgroup=%d resident/CU=%zu\n",
-                         L, (int)RUIN, (int)PREC, (int)fast, (int)prec_occ, n_replicas, cv.total, PREC ? gl.prec_groups : 0, PREC ? gl.prec_static : 0, wpb, best_resident);
-        }
-    }
-    {  // recorded for sf_list_arith_flags only; the kernels' own choice of ruin recreate is the same (sf_mixed_wave.hip: `v2`)
-        const ListModel& lm = ctx->lm;
-        const bool v2_ok = lm.V <= 128 && lm.n_cap <= 32767 && lm.dim <= 32767 && lm.small32 && lm.mat16;  // rv2_model_ok
-        const int ruin_variant = !gl.has_ruin ? 0 : fast ? 3 : !lm.leg16 ? 1 : v2_ok ? 3 : 2;
-        ctx->last_generic_flags = (fast ? SF_GEN_FAST : 0) | (nodeg ? SF_GEN_NODE_GLOBAL : 0) | (gl2.ringd ? SF_GEN_RING32 : 0) |
-                                  (ruin_variant << SF_GEN_RUIN_SHIFT) | ((int32_t)sizeof(VT) << SF_GEN_VT_SHIFT) |
-                                  (RUIN ? SF_GEN_RUIN_INST : 0) | (L << SF_GEN_LEVELS_SHIFT);
-        if (PREC)  // where the precedence constraint's scratch, static graph and trial evaluation went (what the kernel is handed in gl2)
-            ctx->last_generic_flags |= SF_GEN_PREC | (gl.prec_lds ? SF_GEN_PREC_LDS : 0) |
-                                       ((gl.prec_static ? (gl.prec_static_slim ? 2 : 1) : 0) << SF_GEN_PREC_STATIC_SHIFT) |
-                                       ((gl.prec_lds ? gl.prec_groups : 0) << SF_GEN_PREC_GROUPS_SHIFT) | (prec_occ ? SF_GEN_PREC_OCC : 0) |
-                                       (gl.prec_sweep ? SF_GEN_PREC_SWEEP : 0) | (gl.prec_inc ? SF_GEN_PREC_INC : 0);
-    }
-    SearchParams q = p;
-    q.n_launch = n_replicas;
-    HIPCHK(ctx, (launch_tu_mixed<L, (int)sizeof(VT), RUIN, PREC>(trace, fast ? 1 : (prec_occ ? 2 : 0), make_launch(ctx, &q, (n_replicas + wpb - 1) / wpb, 64 * wpb, cv.total * wpb + (PREC ? (size_t)gl.prec_static : 0), &gl2))));
-    return SF_OK;
+    return hipErrorInvalidDeviceFunction;  // (a missing kernel is an error; the plan names built instantiations only)
 }
 static bool has_plain_list_leaves(sf_ctx* ctx) {
     for (auto& s : ctx->selectors)
@@ -2037,15 +1951,8 @@ static int launch_mixed(sf_ctx* ctx, SearchParams& p, int grid, bool trace) {
         gl.plf.leaf = leaf;
         gl.plf.policy = ctx->prec_policy ? 1 : 0;
     }
-    gl.plf.slow = std::getenv("SF_AMD_PLF_SLOW") != nullptr ? 1 : 0;  // read at every launch
-    gl.plf.force64 = std::getenv("SF_AMD_PLF_FORCE64") != nullptr ? 1 : 0;
-    if (!ctx->d_mixed_ring) {
-        int rc = dalloc(ctx, &ctx->d_mixed_ring, (size_t)ctx->R * GL * GRC * 2);
-        if (!rc) rc = dalloc(ctx, &ctx->d_mixed_ringx, (size_t)ctx->R * GL * GRC);
-        if (rc) return rc;
-    }
-    gl.ring = ctx->d_mixed_ring;
-    gl.ringx = ctx->d_mixed_ringx;
+    const GenericKnobs knobs = generic_knobs();
+    gl.plf.slow = knobs.plf_slow, gl.plf.force64 = knobs.plf_force64;
     gl.union_order = ctx->union_order >= 0 ? ctx->union_order : (gl.n > 1 ? SF_UNION_STRATIFIED_RANDOM : SF_UNION_SEQUENTIAL);
     gl.union_custom = union_is_custom(ctx) && gl.n > 1 ? 1 : 0;
     for (int l = 0; l < GL; ++l) gl.weight[l] = 1;
@@ -2056,112 +1963,42 @@ static int launch_mixed(sf_ctx* ctx, SearchParams& p, int grid, bool trace) {
     if (ctx->has_list_model && (ctx->lm.n_cap > 65535 || ctx->lm.dim > 65536))
         return fail(ctx, SF_ERR_UNSUPPORTED, "generic engine packs list elements and positions in 16 bits");
     p.n_leaves = gl.n;
-    // two level counts (2, 4); i16 values, and i8 values for models whose scalar class dominates the LDS slice (a
-    // replica's value array in one byte per entity: job shop 500 x 20 fits 4 waves per CU instead of 3)
     gl.levels = ctx->levels;
     gl.prec = ctx->has_list_model ? ctx->pm : PrecModel{};
-    {  // the Kahn scratch (12 bytes per node: prec_lds_scratch_bytes) goes to LDS while at least 4 replicas still fit a CU (up to 36 KiB = 3,072 nodes)
-        const bool no_lds = std::getenv("SF_AMD_PREC_HBM") != nullptr;  // diagnostics / parity tests: force the HBM scratch (read at every launch)
-        // ... and beyond that whenever ONE replica per CU still fits: 10,000 nodes (job shop 500 x 20) run 1.7 x the rate of the HBM scratch with
-        // half the replicas (profiles/r05_prec_eval_ab.txt).  SF_AMD_PREC_LDS_MAX_KB caps the scratch (36 = the round-4 rule)
-        size_t lds_max = SF_LDS_BUDGET;
-        if (const char* e = std::getenv("SF_AMD_PREC_LDS_MAX_KB")) lds_max = (size_t)std::atoi(e) * 1024;
-        bool fits = gl.prec.on && !no_lds && prec_lds_scratch_bytes(gl.prec.n) <= lds_max && gl.prec.n < 65535;
-        if (fits && prec_lds_scratch_bytes(gl.prec.n) > 36 * 1024) {  // the whole slice of a replica with the scratch in it (2-byte values: the larger carve)
-            const int ns = ctx->has_scalar_model ? ctx->sm.n : 0;
-            const bool tables = ctx->has_scalar_model && ctx->sm.tables();
-            const GCarve<int16_t> cv(ns, ctx->lm.V, ctx->lm.n_cap, gl.has_nearby ? ctx->lm.dim : 0, gl.kopt_nearby, gl.n, gl.has_ruin ? (ctx->lm.leg16 ? 2 : 1) : 0,
-                                     ctx->lm.dim, gl.prec.n, tables ? ctx->sm.n_values : 0, tables && ctx->sm.run_level >= 0 ? ctx->sm.run_P : 0, 0, false);
-            fits = cv.total + 1024 <= SF_LDS_BUDGET;
-        }
-        gl.prec_lds = fits ? 1 : 0;
-        // the incremental trial refresh is parity-complete but SLOWER than one full evaluation per trial on every job shop measured
-        // (profiles/r03f_precedence.txt): opt-in for the parity tests and further work
-        gl.prec_inc = std::getenv("SF_AMD_PREC_INC") != nullptr ? 1 : 0;
-        // lane-per-trial sweep (prec_trial_sweep64): the default with the scratch in HBM; SF_AMD_PREC_NO_SWEEP = one full evaluation per trial
-        // the constraint's static graph (durations, fixed successors / predecessors, in-degrees, owners) once per workgroup in LDS: every Kahn
-        // round reads it behind a dependent LDS access (SF_AMD_PREC_STATIC_HBM = leave it in HBM / L1)
-        gl.prec_static = 0, gl.prec_static_slim = 0;
-        if (gl.prec.on && gl.prec_lds && std::getenv("SF_AMD_PREC_STATIC_HBM") == nullptr) {
-            const size_t b = prec_static_bytes(gl.prec.n, gl.prec.n_edges, gl.prec.owner != nullptr);
-            if (b <= 16 * 1024) gl.prec_static = (int32_t)b;
-            // beyond that: the node records, fixed in-degrees and owners alone (what every evaluation reads per node; the rounds of a 1,000-node
-            // evaluation waited on an L2 round trip for the record otherwise).  SF_AMD_PREC_STATIC_SLIM=0 leaves them in HBM
-            const size_t sb = prec_static_slim_bytes(gl.prec.n, gl.prec.owner != nullptr);
-            const char* se = std::getenv("SF_AMD_PREC_STATIC_SLIM");
-            if (!gl.prec_static && sb <= 40 * 1024 && !(se && std::atoi(se) == 0)) gl.prec_static = (int32_t)sb, gl.prec_static_slim = 1;
-            // the shared copy sits beside the replicas' slices in the workgroup's LDS: when one slice with the Kahn scratch in it leaves no room for
-            // the copy (about 3,100 - 3,400 nodes without owners plus a large list slice), the copy stays in HBM instead of an over-size launch
-            if (gl.prec_static) {
-                const int ns2 = ctx->has_scalar_model ? ctx->sm.n : 0;
-                const bool tables2 = ctx->has_scalar_model && ctx->sm.tables();
-                const GCarve<int16_t> cv2(ns2, ctx->lm.V, ctx->lm.n_cap, gl.has_nearby ? ctx->lm.dim : 0, gl.kopt_nearby, gl.n, gl.has_ruin ? (ctx->lm.leg16 ? 2 : 1) : 0,
-                                          ctx->lm.dim, gl.prec.n, tables2 ? ctx->sm.n_values : 0, tables2 && ctx->sm.run_level >= 0 ? ctx->sm.run_P : 0, 0, false);
-                if (cv2.total + 1024 + (size_t)gl.prec_static > SF_LDS_BUDGET) gl.prec_static = 0, gl.prec_static_slim = 0;
-            }
-        }
-        // grouped trial evaluator (sf_prec_group.h): T trials per wavefront with private LDS scratch.  SF_AMD_PREC_GROUPS = 0 / 2 / 4 / 8 / 16
-        gl.prec_groups = 0;
-        if (gl.prec.on && gl.prec_lds && gl.prec_static && !gl.prec_static_slim) {  // (its node records live in the FULL shared static copy)
-            // default: as many trials per wave as the graph's width allows -- a Kahn round pops at most one node per list, so lane groups of
-            // the largest power of two <= the list count (5 machines: 4 lanes, 16 trials; 10: 8 lanes, 8 trials) -- halved until the scratch
-            // fits: under 14 KB, or the replica's precedence state (scratch + 16 B per node of Kahn arrays + ~2.5 KB) under 20 KB, which
-            // keeps eight replicas on a CU.  200 nodes: 4; 300: 2; 1,000: off (50 x 20: 34.8 -> 26.0 M moves/s with 2)
-            int T = 0;
-            {
-                int g = 1;
-                while (g * 2 <= (ctx->lm.V > 2 ? ctx->lm.V : 2)) g *= 2;
-                for (int t = 64 / g > 16 ? 16 : 64 / g; t >= 2; t >>= 1) {
-                    const size_t b = pgrp_bytes(gl.prec.n, t, ctx->lm.V);
-                    if (b <= 14 * 1024 || b + (size_t)gl.prec.n * 16 + 2560 <= 20 * 1024) {
-                        T = t;
-                        break;
-                    }
-                }
-            }
-            if (const char* e = std::getenv("SF_AMD_PREC_GROUPS")) {
-                T = std::atoi(e);
-                if (T != 2 && T != 4 && T != 8 && T != 16) T = 0;
-                while (T > 1 && pgrp_bytes(gl.prec.n, T, ctx->lm.V) > 40 * 1024) T >>= 1;
-            }
-            gl.prec_groups = T > 1 ? T : 0;
-        }
-        gl.prec_sweep = (gl.prec.on && !gl.prec_lds && !gl.prec_inc && std::getenv("SF_AMD_PREC_NO_SWEEP") == nullptr) ? 1 : 0;
-        if (gl.plf.on) gl.prec_inc = gl.prec_sweep = 0;  // the critical-path leaf re-evaluates in the main scratch arrays: one full evaluation per trial
-        if (gl.prec_sweep && !ctx->pm.elane) {  // [R][n][64] earliest starts of the trials in flight
-            int rc = dalloc(ctx, &ctx->pm.elane, (size_t)ctx->R * (size_t)ctx->pm.n * 64);
-            if (rc) return rc;
-            gl.prec.elane = ctx->pm.elane;
+    const GenericPlan pl = plan_generic_launch(generic_shape(ctx, p, gl, grid, trace), knobs);
+    if (pl.err) return fail(ctx, pl.err, pl.msg);
+    // buffers allocated by the first launch that needs them (a refused launch allocates none)
+    if (!ctx->d_mixed_ring) {
+        int rc = dalloc(ctx, &ctx->d_mixed_ring, (size_t)ctx->R * GL * GRC * 2);
+        if (!rc) rc = dalloc(ctx, &ctx->d_mixed_ringx, (size_t)ctx->R * GL * GRC);
+        if (rc) return rc;
+    }
+    if (pl.ring32 && !ctx->d_mixed_ringd)
+        if (int rc = dalloc(ctx, &ctx->d_mixed_ringd, (size_t)ctx->R * GL * GRC * 2)) return rc;
+    if (pl.nodeg && !ctx->d_node_tab32)
+        if (int rc = dalloc(ctx, &ctx->d_node_tab32, (size_t)ctx->R * ctx->lm.dim)) return rc;
+    if (pl.prec_sweep && !ctx->pm.elane)  // [R][n][64] earliest starts of the trials in flight
+        if (int rc = dalloc(ctx, &ctx->pm.elane, (size_t)ctx->R * (size_t)ctx->pm.n * 64)) return rc;
+    gl.ring = ctx->d_mixed_ring, gl.ringx = ctx->d_mixed_ringx;
+    gl.ringd = pl.ring32 ? ctx->d_mixed_ringd : nullptr;
+    if (pl.nodeg) gl.node_tab = ctx->d_node_tab32;
+    gl.prec.elane = ctx->pm.elane;
+    gl.prec_lds = pl.prec_lds, gl.prec_inc = pl.prec_inc, gl.prec_sweep = pl.prec_sweep;
+    gl.prec_static = pl.prec_static, gl.prec_static_slim = pl.prec_static_slim, gl.prec_groups = pl.prec_groups;
+    if (knobs.debug_launch) {  // diagnostics: the launch shape, once per change
+        static size_t last = 0;
+        const size_t key = (size_t)pl.slice * 131 + (size_t)pl.wpb * 7 + (size_t)grid + (pl.mode == 2 ? 1 : 0);
+        if (key != last) {
+            last = key;
+            std::fprintf(stderr, "[sf] generic engine launch: L=%d ruin=%d prec=%d fast=%d prec_occ=%d replicas=%d LDS/replica=%zu B (prec groups %d, static %d B) waves/workgroup=%d resident/CU=%zu\n",
+                         pl.levels, pl.ruin_inst, pl.prec, (int)(pl.mode == 1), (int)(pl.mode == 2), grid, (size_t)pl.slice, pl.prec ? pl.prec_groups : 0, pl.prec ? pl.prec_static : 0, pl.wpb, (size_t)pl.resident);
         }
     }
-    if (gl.prec.on && gl.has_ruin) {  // ruin leaf on a precedence model (i16 values)
-        if (ctx->levels <= 2)
-            return launch_mixed_t<2, int16_t, true, true>(ctx, p, gl, grid, trace);
-        return launch_mixed_t<4, int16_t, true, true>(ctx, p, gl, grid, trace);
-    }
-    if (gl.prec.on) {  // ListPrecedenceMakespanConstraint: its own instantiations
-        if (ctx->has_scalar_model && ctx->sm.n_values <= 127 && ctx->sm.n >= 1024) {  // one-byte value array (C4: 4 waves per CU instead of 3)
-            if (ctx->levels <= 2)
-                return launch_mixed_t<2, int8_t, false, true>(ctx, p, gl, grid, trace);
-            return launch_mixed_t<4, int8_t, false, true>(ctx, p, gl, grid, trace);
-        }
-        if (ctx->levels <= 2)
-            return launch_mixed_t<2, int16_t, false, true>(ctx, p, gl, grid, trace);
-        return launch_mixed_t<4, int16_t, false, true>(ctx, p, gl, grid, trace);
-    }
-    if (gl.has_ruin) {  // the ruin leaf has its own instantiations (i16 values only)
-        if (ctx->levels <= 2)
-            return launch_mixed_t<2, int16_t, true>(ctx, p, gl, grid, trace);
-        return launch_mixed_t<4, int16_t, true>(ctx, p, gl, grid, trace);
-    }
-    if (ctx->has_scalar_model && ctx->sm.n_values <= 127 && ctx->sm.n >= 1024) {
-        if (ctx->levels <= 2)
-            return launch_mixed_t<2, int8_t>(ctx, p, gl, grid, trace);
-        return launch_mixed_t<4, int8_t>(ctx, p, gl, grid, trace);
-    }
-    if (ctx->levels <= 2)
-        return launch_mixed_t<2, int16_t>(ctx, p, gl, grid, trace);
-    return launch_mixed_t<4, int16_t>(ctx, p, gl, grid, trace);
+    ctx->last_generic_flags = pl.flags;  // (sf_list_arith_flags: what the kernel is handed in gl; its own choice of ruin recreate is the same, sf_mixed_wave.hip: `v2`)
+    SearchParams q = p;
+    q.n_launch = grid;  // (`grid` = the replicas of this launch)
+    HIPCHK(ctx, dispatch_tu_mixed(pl, trace, make_launch(ctx, &q, pl.grid, pl.block, (size_t)pl.lds, &gl)));
+    return SF_OK;
 }
 
 extern "C" {
@@ -2430,6 +2267,25 @@ int32_t sf_download_scalar(sf_ctx* ctx, int32_t replica, int32_t d, int32_t var,
 }
 
 }  // extern "C"
+
+// Diagnostic export, not part of the ABI header: the generic engine's launch plan for a shape and a set of switches, without a device
+// or a context (tests/test_generic_plan.py).  The three arrays are the int32 fields of GenericShape, GenericKnobs and GenericPlan
+// (sf_mixed_plan.h) in declaration order, `kind` taking GL words and the plan stopping before `msg`; the counts guard against drift.
+// Returns the plan's refusal code; `msg`, when given, receives the refusal's text (a string constant) or nullptr.
+extern "C" int32_t sf_debug_generic_plan(const int32_t* shape, int32_t n_shape, const int32_t* knobs, int32_t n_knobs, int32_t* plan, int32_t n_plan, const char** msg) {
+    constexpr size_t plan_bytes = offsetof(GenericPlan, msg);
+    if (!shape || !knobs || !plan || n_shape * 4 != (int)sizeof(GenericShape) || n_knobs * 4 != (int)sizeof(GenericKnobs) || n_plan * 4 != (int)plan_bytes)
+        return SF_ERR_INVALID;
+    GenericShape s;
+    GenericKnobs k;
+    std::memcpy(&s, shape, sizeof s);
+    std::memcpy(&k, knobs, sizeof k);
+    if (s.n_leaves < 0 || s.n_leaves > GL) return SF_ERR_INVALID;
+    const GenericPlan pl = plan_generic_launch(s, k);
+    std::memcpy(plan, &pl, plan_bytes);
+    if (msg) *msg = pl.msg;
+    return pl.err;
+}
 
 #ifdef SF_PHASE_PROFILE
 extern "C" int32_t sf_debug_ruin_phases(uint64_t* out8) {  // diagnostic builds only: shader clocks inside ruin_recreate

@@ -313,7 +313,7 @@ namespace sf {
 // diagnostics (register-pressure bisection): -DSF_DBG_KINDS=<mask> compiles the generators of the masked leaf kinds out
 // MODE 1 additionally compiles out the generators / evaluators no default list policy of a slot with a distance meter declares (round 4):
 // plain list change / swap (4, 8), the full 3-opt enumeration (the `1` bit below), list permute (8192) -- the host takes FAST only for
-// unions of nearby change / swap, sublist change / swap, reverse, distance-pruned 3-opt and ruin (launch_mixed_t).
+// unions of nearby change / swap, sublist change / swap, reverse, distance-pruned 3-opt and ruin (plan_generic_launch).
 #ifdef SF_DBG_KINDS
 #define DBGK(k) ((((SF_DBG_KINDS) & (k)) == 0) && (!FAST || ((k) & (16 | 32 | 64 | 128 | 256 | 512)) != 0))
 #else
@@ -325,11 +325,11 @@ namespace sf {
 // MODE 2 (PREC instantiations, untraced): the same code built for four 4-wave workgroups per CU (128 registers per lane).  A precedence
 // trial is one replica's serial chain of Kahn rounds, so a CU that can hold more than eight small replicas (LDS slice permitting) hides
 // that latency with more of them: nine-leaf policy on a 20 x 10 job shop 38.3 M moves/s at 2,048 replicas -> 54.7 M at 4,096, 10 x 5
-// 102.7 M (profiles/r03w_prec_occupancy.txt).  The host picks per launch (launch_mixed_t): untraced, no grouped evaluator, more than 2,048
+// 102.7 M (profiles/r03w_prec_occupancy.txt).  The host picks per launch (plan_generic_launch): untraced, no grouped evaluator, more than 2,048
 // replicas and a slice of at most 17,948 bytes (nine or more replicas per CU).  Since the scratch shrank to 12 bytes per node the 50 x 20
 // shop under the nine-leaf policy is inside that (16,080-byte slice, ten per CU): sf_list_arith_flags reports MODE 2 for it from 2,049
 // replicas on (tests/test_gpu_prec_placement.py); a general graph of 1,218 nodes on eight lists (17,952 bytes) is the first that keeps MODE 0.
-// Static LDS of one workgroup, which the host's workgroup-shape loop adds to the dynamic slices (launch_mixed_t; read back from the code
+// Static LDS of one workgroup, which the host's workgroup-shape loop adds to the dynamic slices (plan_generic_launch; read back from the code
 // objects' group_segment_fixed_size): the annealing state s_sa, and in the PREC instantiations the broadcast words s_psw_info, s_prec_info
 // and s_plf_info (the others drop them unused).  The FAST kernels have none.  A new __shared__ array belongs in these sums.
 constexpr size_t SF_MIXED_STATIC_LDS = 4 * SA_WORDS * sizeof(uint64_t);

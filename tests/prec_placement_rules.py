@@ -1,6 +1,6 @@
-"""The host's placement rules for a precedence model's fused launch (csrc/sf_api.hip: launch_mixed), restated once for the GPU tests
+"""The host's placement rules for a precedence model's fused launch (csrc/sf_mixed_plan.h: plan_generic_launch), restated once for the GPU tests
 that assert the placement the library recorded (test_gpu_prec_placement.py, test_gpu_precedence.py, test_gpu_precedence_leaf.py).
-n nodes, E valid fixed edges, V lists; all integer.  Not a test module."""
+n nodes, E valid fixed edges, V lists; all integer.  test_generic_plan.py checks this restatement against the library.  Not a test module."""
 
 
 def a16(x):

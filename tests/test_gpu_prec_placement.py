@@ -1,5 +1,5 @@
 """GPU parity tests (through the C ABI) on both sides of every gate by which the host places a precedence (job-shop makespan) model's
-fused launch (csrc/sf_api.hip: launch_mixed, launch_mixed_t).  Every case builds a model on one side of one gate, runs a fused launch,
+fused launch (csrc/sf_mixed_plan.h: plan_generic_launch).  Every case builds a model on one side of one gate, runs a fused launch,
 asserts the placement the library recorded (sf_list_arith_flags -> GpuScoreDirector.arith_flags: PREC instantiation, Kahn scratch in
 LDS, static copy none / full / slim, grouped trials T, MODE 2, sweep, incremental refresh, RUIN instantiation, level template, value
 bytes), then compares with the CPU oracle in integer equality: full score, fresh score and evaluate_each of a scheduled, a reversed
@@ -17,7 +17,7 @@ Edge sizes, from the host's own formulas (n nodes, E valid fixed edges, V lists;
   slim static copy    prec_static_slim_bytes = (owner ? 16 : 12) n + 16 <= 40,960: owners 2,559 in / 2,560 out; none 3,412 in / 3,413 out.
   cv2 fit             the copy is dropped when slice + 1,024 + copy > 162,816: 3,400 nodes without owners (copy 40,816) on 8 lists with an
                       element capacity of 39,648 (slice 120,976: in, sum 162,816) / 39,649 (out).
-  groups' fit         launch_mixed_t repeats that test on the slice WITH the grouped evaluator's scratch and halves T until it passes:
+  groups' fit         the plan repeats that test on the slice WITH the grouped evaluator's scratch and halves T until it passes:
                       428 nodes, 5 lists (T = 2, scratch 14,304; copy 13,720): capacity 63,888 in (162,808), 63,889 out (T = 0);
                       SF_AMD_PREC_GROUPS=16 on 300 nodes, 3 lists: 57,928 keeps 8 / 57,929 -> 4; 65,160 keeps 4 / 65,161 -> 2.
   grouped evaluator   needs the full copy.  g = largest power of two <= max(V, 2), t = min(16, 64 / g), halved while
@@ -28,7 +28,8 @@ Edge sizes, from the host's own formulas (n nodes, E valid fixed edges, V lists;
   MODE 2              untraced, T = 0, replicas > 2,048, 163,840 / (slice + 256) > 8 <=> slice <= 17,948.  30 x 20 shop: 9,424;
                       50 x 20 nine-leaf: 16,080; 8 lists, two leaves: n = 1,217 -> 17,936 (in), 1,218 -> 17,952 (out).
   one-byte values     n_values <= 127 and >= 1,024 scalar entities, in the L = 2 and the L = 4 template.
-The carve totals were computed with the host's GCarve on the host; the asserted placements fail loudly if the carve changes.
+The carve totals were computed with the host's GCarve on the host, and test_generic_plan.py asserts them there (no GPU); the asserted
+placements fail loudly if the carve changes.
 
 The host-driven entry points (sf_evaluate_all, sf_step_evaluate, sf_apply) read none of the SF_AMD_PREC_* variables: their Kahn scratch is
 the model's HBM arrays always (one wavefront per replica / record, list copies in LDS), so there is no placement to record for them."""
@@ -280,7 +281,7 @@ def test_static_copy_dropped_when_the_slice_leaves_no_room(oracle, capacity, sta
 def test_groups_scratch_overflow_halves_the_groups(oracle, monkeypatch, forced, n, V, capacity, T):
     """The fit test of the static copy runs before the grouped evaluator is chosen, on a slice without its scratch, so the real carve can
     pass a CU's LDS where the estimate fitted.  Such a launch used to be refused (SF_ERR_UNSUPPORTED: "one replica's LDS slice ... exceeds
-    a CU's 160 KiB" / "model does not fit one wave's LDS slice"); launch_mixed_t now repeats the same fit test (slice + 1,024 + copy <=
+    a CU's 160 KiB" / "model does not fit one wave's LDS slice"); plan_generic_launch now repeats the same fit test (slice + 1,024 + copy <=
     162,816) on its own carve and halves the groups until it passes; the copy stays (without groups the slice is the one the estimate
     passed).  It is reachable under DEFAULT settings by a small graph on a list class of a large element capacity:
       428 nodes, 5 lists, 214 edges, owners: full copy 28 n + 8 E + 24 = 13,720; T = 2, scratch 14,304.  Capacity 63,888: slice without

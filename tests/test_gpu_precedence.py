@@ -35,7 +35,7 @@ LEAF_BITS = {"list_change": 4, "list_swap": 8, "list_reverse": 64, "sublist_chan
 
 
 def _assert_placement(d, mode, n, E, V, owner=True, lds_cap_kb=None, slim=True, whole_slice_fits=None, **over):
-    """The last fused launch went where the scratch_mode parameter says (sf_list_arith_flags; the host's rules in launch_mixed, restated in
+    """The last fused launch went where the scratch_mode parameter says (sf_list_arith_flags; the host's rules in plan_generic_launch, restated in
     prec_placement_rules): n nodes, E fixed edges, V lists.  lds: scratch in LDS and the grouped evaluator at the default rule's T;
     lds_one_trial: T = 0; lds_groups16: the forced T after the 40 KiB halving; lds_static_hbm: no static copy, so T = 0; hbm: the sweep;
     hbm_full: neither sweep nor incremental refresh; hbm_incremental: the refresh.  Above 3,072 nodes (36 KiB of scratch) the whole-slice

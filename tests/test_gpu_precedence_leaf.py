@@ -41,7 +41,7 @@ def scratch(request):
 
 
 def _assert_placement(d, mode, p, tables=True, owner=True, **over):
-    """The last fused launch went where the `scratch` parameter says (sf_list_arith_flags; the host's rules in launch_mixed, restated in
+    """The last fused launch went where the `scratch` parameter says (sf_list_arith_flags; the host's rules in plan_generic_launch, restated in
     prec_placement_rules).  lds (and the two parameters that only change the leaf's own code paths): scratch in LDS, the grouped evaluator
     at the default rule's T; lds_one_trial: T = 0; lds_groups2 / lds_groups16: the forced T after the 40 KiB halving; hbm: scratch in
     HBM -- with the sweep, unless the launch carries the critical-path leaf's per-replica tables (the leaf, the slot's policy or a ruin
