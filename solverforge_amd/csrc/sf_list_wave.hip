@@ -658,9 +658,33 @@ __device__ __forceinline__ bool eval_list_move_small(const ListModel& m, const u
 // nothing is tested here.  Written for the scalar unit's sake (the kernel's bound): a per-lane predicate is a v_cmp into an SGPR pair, every
 // `&&` / `||` of two predicates one scalar instruction, every compare-then-select a wait state on gfx950; so neighbours are addressed with
 // min() arithmetic, and `chg` arrives as an integer (1 = ListChange, 0 = ListSwap).
+// LevelWords: which score level each constraint feeds, as all-ones / zero words made once per launch (level_words).  The empty asm keeps
+// them words: left to itself the compiler turns `k == m.cap_level ? ~0 : 0` back into a compare, i.e. a 64-bit lane mask per (level,
+// constraint) -- eight spill lanes read back in every replay batch, and a select with a wait state each.
+template <int L>
+struct LevelWords {
+    uint32_t wc[L], wd[L];  // capacity / distance share of level k
+    uint32_t has_cap;       // the capacity constraint exists (m.cap_level >= 0)
+};
+template <int L, bool USED>  // (USED = false: a kernel that never prices with eval_generated_small -- nothing is pinned)
+__device__ __forceinline__ LevelWords<L> level_words(const ListModel& m) {
+    LevelWords<L> w;
+#pragma unroll
+    for (int k = 0; k < L; ++k) {
+        w.wc[k] = uni(k == m.cap_level ? 0xFFFFFFFFu : 0u);
+        w.wd[k] = uni(k == m.dist_level ? 0xFFFFFFFFu : 0u);
+        if constexpr (USED) {
+            asm volatile("" : "+s"(w.wc[k]));
+            asm volatile("" : "+s"(w.wd[k]));
+        }
+    }
+    w.has_cap = uni(m.cap_level >= 0 ? 1u : 0u);
+    if constexpr (USED) asm volatile("" : "+s"(w.has_cap));
+    return w;
+}
 template <int L, class LT, bool M16 = false, class OT = uint32_t>
-__device__ __forceinline__ void eval_generated_small(const ListModel& m, const uint16_t* visits, const OT* off, const LT* load, uint32_t c, uint32_t a,
-                                                     uint32_t i, uint32_t b, uint32_t j, int32_t (&dv)[L]) {
+__device__ __forceinline__ void eval_generated_small(const ListModel& m, const LevelWords<L>& lw, const uint16_t* visits, const OT* off, const LT* load, uint32_t c,
+                                                     uint32_t a, uint32_t i, uint32_t b, uint32_t j, int32_t (&dv)[L]) {
     const uint32_t oa = off[a], la = off[a + 1] - oa;
     const uint32_t ob = off[b], lb = off[b + 1] - ob;
     const uint32_t depot = (uint32_t)m.depot;
@@ -695,7 +719,7 @@ __device__ __forceinline__ void eval_generated_small(const ListModel& m, const u
     const uint32_t m3 = leg(vq, nb);
     const uint32_t m2 = leg(adj ? vq : pb, adj ? nb : vq);
     int32_t d_cap = 0;
-    if (m.cap_level >= 0) {
+    if (lw.has_cap != 0u) {
         const int32_t dx = m.demand[x];
         const int32_t dyq = m.demand[vq];
         const int32_t dy = chg ? 0 : dyq;
@@ -709,13 +733,10 @@ __device__ __forceinline__ void eval_generated_small(const ListModel& m, const u
     const uint32_t minus = m0 + m1 + ((chg && !intra && lb == 0) ? 0u : m2) + (ca ? 0u : m3);
     const int32_t d_dist = (int32_t)(plus - minus);
     // penalties: score level -= weight * delta(penalty sum); a level's share is picked with a 32-bit all-ones / zero word per (level, constraint) --
-    // two wave-uniform words instead of a lane mask in a scalar register pair and a select each
+    // two wave-uniform words (LevelWords) instead of a lane mask in a scalar register pair and a select each
     const int32_t tc = -((int32_t)m.cap_weight * d_cap), td = -((int32_t)m.dist_weight * d_dist);
 #pragma unroll
-    for (int k = 0; k < L; ++k) {
-        const uint32_t wc = k == m.cap_level ? 0xFFFFFFFFu : 0u, wd = k == m.dist_level ? 0xFFFFFFFFu : 0u;
-        dv[k] = (int32_t)(((uint32_t)tc & wc) + ((uint32_t)td & wd));
-    }
+    for (int k = 0; k < L; ++k) dv[k] = (int32_t)(((uint32_t)tc & lw.wc[k]) + ((uint32_t)td & lw.wd[k]));
 }
 
 // Per-leaf cursor state of one step.  The NEXT source of the leaf is always resolved ahead of use
@@ -732,6 +753,28 @@ struct LeafCursor {
     uint32_t pv;          // per lane: (source position | source element << 16) of offset vbase + lane of entity rank vk
     uint32_t cend;        // offsets o < cend of the current entity are served by `pv` as it stands (0 = nothing cached): resolve()'s one-compare fast path
 };
+
+// The kernel's argument block as it lies in the kernarg segment (by-value structs in declaration order, each at its own alignment), and a
+// view of it that is read AGAIN at the point of use.  A field taken from the by-value arguments is loaded in the kernel's prologue and then
+// carried -- in a scalar register or in a spill lane -- to wherever it is used; the fields that are used once per step or once per launch
+// (history, counters and write-back pointers, seeds, budgets) are read through cold_args() instead: one scalar load where the value is
+// needed, nothing live across the fill and replay loops.  (The empty asm hides the pointer's origin from the optimiser, which would otherwise
+// merge the load with the prologue's and carry the value after all.)
+// That WaveArgs and the segment have the same layout rests on the AMDGPU kernarg ABI: the explicit arguments start at offset 0 of the segment,
+// in declaration order, each at its own ABI alignment -- the rule that lays out the members of a struct.  It holds only while the members of
+// WaveArgs ARE the kernel's parameters, type by type and in order: the static_assert below the kernel refuses to compile anything else (a
+// parameter added, removed or moved would otherwise turn every write-back pointer into garbage without a word from the compiler).
+struct WaveArgs {
+    ListModel m;
+    SearchParams p;
+    NbrIndex nb;
+};
+typedef const __attribute__((address_space(4))) WaveArgs* ColdArgs;
+__device__ __forceinline__ ColdArgs cold_args() {
+    uint64_t u = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(u));
+    return (ColdArgs)u;
+}
 
 // MODE 1 (FAST): compile-time specialisation for the default list policy (nearby change + nearby swap union,
 // LateAcceptance + AcceptedCount, committed steps) — fewer live scalars and branches in the hot loops.
@@ -754,6 +797,10 @@ struct LeafCursor {
 template <int L, bool TRACE, int MODE, bool COMPACT = false, int WPE = SF_WAVES_PER_EU, bool NODEG = false>
 __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m, SearchParams p, NbrIndex nb) {
     constexpr bool FAST = MODE >= 1, SMALL = MODE == 2;
+// A cold field of `p` / `m`: the FAST + SMALL kernels -- the ones whose bound is the scalar unit -- read it from the argument block where it
+// is used, the others from the by-value structs.  (Local to this kernel: the macros name its `SMALL`, `p` and `m`, and end with it.)
+#define SF_COLD_P(f) (SMALL ? cold_args()->p.f : p.f)
+#define SF_COLD_M(f) (SMALL ? cold_args()->m.f : m.f)
     static_assert(!COMPACT || SMALL, "COMPACT stores loads in 32 bits: MODE 2 only");
     static_assert(!NODEG || COMPACT, "NODEG: the 16-bit table of the COMPACT layout");
     using LT = typename std::conditional<COMPACT, int32_t, int64_t>::type;
@@ -780,7 +827,12 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
     const bool annealing = !FAST && acceptor == 3;
     if constexpr (!FAST)
         if (annealing) sa_load(saw, p.sa, r, lane);
-    const uint64_t desc0 = (uint64_t)p.leaf[0].descriptor, desc1 = n_leaves > 1 ? (uint64_t)p.leaf[1].descriptor : 0;
+    // the leaves' descriptor indices as the salts take them (sign-extended to 64 bits).  SMALL carries them as the 32-bit words they are and
+    // widens where a salt is formed; the general kernels keep the widened pair (their register allocation is left as it was)
+    const int32_t desc0_w = p.leaf[0].descriptor, desc1_w = n_leaves > 1 ? p.leaf[1].descriptor : 0;
+    const uint64_t desc0_q = SMALL ? 0 : (uint64_t)p.leaf[0].descriptor, desc1_q = (!SMALL && n_leaves > 1) ? (uint64_t)p.leaf[1].descriptor : 0;
+    auto desc0 = [&]() -> uint64_t { return SMALL ? (uint64_t)(int64_t)desc0_w : desc0_q; };
+    auto desc1 = [&]() -> uint64_t { return SMALL ? (uint64_t)(int64_t)desc1_w : desc1_q; };
 
     const WCarve cv(V, m.n_cap, m.dim, (int)(K0 > K1 ? K0 : K1), COMPACT, NODEG);
     const uint32_t RCM = cv.rc - 1;
@@ -809,6 +861,8 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
     uint32_t* rtab = (uint32_t*)(mem + cv.rtab);
     uint16_t* route_at = (uint16_t*)(mem + cv.routeat);  // [leaf][rank] -> route
 
+    // (SMALL uses the replica's base pointers for the load below only and forms them again at the write-back, from the argument block:
+    // nothing of them is carried through the step loop)
     uint32_t* g_visits = m.visits + (size_t)r * m.n_cap;
     uint32_t* g_off = m.off + (size_t)r * (V + 1);
     int64_t* g_load = m.load + (size_t)r * V;
@@ -843,10 +897,10 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
     // per-launch counters in 32 bits (wave-uniform: scalar registers), folded into the replica's 64-bit sf_stats words
     // before they can wrap (flush_stats): a long fixed-step launch never loses counts
     uint32_t st_steps = 0, st_gen = 0, st_acc = 0, st_applied = 0, st_calc = 0, st_scored = 0, st_sources = 0;
-    uint64_t steps_run = 0;
+    uint64_t steps_run = 0;  // (general kernels; SMALL reads the number of steps off the loop counter instead)
     auto flush_stats = [&]() {
         if (lane == 0) {
-            uint64_t* gs = p.stats + (size_t)r * SF_STATS_WORDS;
+            uint64_t* gs = SF_COLD_P(stats) + (size_t)r * SF_STATS_WORDS;
             gs[0] += st_steps;
             gs[1] += st_gen;
             gs[2] += st_gen;
@@ -857,7 +911,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
             gs[7] += st_scored;
             gs[8] += st_sources;
         }
-        steps_run += st_steps;
+        if constexpr (!SMALL) steps_run += st_steps;
         st_steps = st_gen = st_acc = st_applied = st_calc = st_scored = st_sources = 0;
     };
     uint64_t trace_n = 0;
@@ -868,6 +922,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
     const uint64_t lanebit = 1ULL << lane;
     PH_DECL
 
+    const LevelWords<L> lvl = level_words<L, SMALL>(m);
     bool best_pending = false;  // working == best, snapshot not yet written (see sf_scalar_kernels.hip: deferred clone)
     const FastMod fm_V = make_fastmod(V > 0 ? (uint32_t)V : 1u);
     const FastMod fm_V1 = make_fastmod(V > 1 ? (uint32_t)V - 1u : 1u);
@@ -876,8 +931,10 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
     const bool use_cm = V >= 2 && V <= 128;
     const uint64_t cm_lo = use_cm ? __ballot(lane >= 1 && lane < (uint32_t)V && gcd_u32(lane, (uint32_t)V) == 1) : 0ull;
     const uint64_t cm_hi = use_cm ? __ballot(lane + 64 < (uint32_t)V && gcd_u32(lane + 64, (uint32_t)V) == 1) : 0ull;
-    for (int64_t step = 0; step < p.n_steps; ++step) {
+    int64_t step = 0;  // SMALL, after the loop: the number of steps that ran (a move budget ends the launch early)
+    for (; step < SF_COLD_P(n_steps); ++step) {
         PH(7)
+        ISA_MARK("prologue_begin");
         // ---- (A) step start (step.rs:60-74) -------------------------------------------------
         uint64_t sidx, sseed;
         if (dry_run) {
@@ -886,10 +943,12 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
         } else {
             sidx = step_index0 + (uint64_t)step;
             const uint64_t draw = seed_draws0 + (uint64_t)step;
-            if (p.explicit_seeds && (int64_t)draw < p.n_explicit)
-                sseed = p.explicit_seeds[(size_t)r * p.n_explicit + draw];
+            const uint64_t* const explicit_seeds = SF_COLD_P(explicit_seeds);
+            const int64_t n_explicit = SF_COLD_P(n_explicit);
+            if (explicit_seeds && (int64_t)draw < n_explicit)
+                sseed = explicit_seeds[(size_t)r * n_explicit + draw];
             else
-                sseed = step_seed(p.random_seed + (uint64_t)r, draw);
+                sseed = step_seed(SF_COLD_P(random_seed) + (uint64_t)r, draw);
         }
         sidx = uni64(sidx);
         sseed = uni64(sseed);
@@ -899,8 +958,9 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
         for (int k = 0; k < L; ++k) late.v[k] = 0;
         const int la_slot = la_cursor;  // LateAcceptance history slot of this step
         if (acceptor == 1 || acceptor == 4) {
+            const int64_t* const lh = SF_COLD_P(la_hist) + ((size_t)r * SF_COLD_P(la_size) + la_slot) * 4;
 #pragma unroll
-            for (int k = 0; k < L; ++k) late.v[k] = (int64_t)uni64((uint64_t)p.la_hist[((size_t)r * p.la_size + la_slot) * 4 + k]);
+            for (int k = 0; k < L; ++k) late.v[k] = (int64_t)uni64((uint64_t)lh[k]);
         }
         ScoreV<L> dla_thr = late;  // DiversifiedLateAcceptance: best step score of the phase minus its tolerance band
         if (acceptor == 4) {
@@ -910,7 +970,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
             dla_thr = dla_threshold<L>(db, p.dla_tolerance);
         }
         int has_best = 0;
-        uint64_t equal_count = 0;
+        typename std::conditional<SMALL, uint32_t, uint64_t>::type equal_count = 0;  // (SMALL: 32 bits -- a step consumes far fewer than 2^32 candidates; reservoir_pick hashes it as 64 bits)
         uint32_t accepted = 0, pulls = 0;
         ScoreV<L> best;
 #pragma unroll
@@ -945,7 +1005,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
         uint32_t hashed = 0;  // lane l < 5: remainder of mixed_seed(salt_l) by its divisor
         const bool lane_hash = FAST && use_cm;
         if (lane_hash) {
-            const uint64_t es0 = SALT_NEARBY_CHANGE_ENTITY ^ desc0, es1 = SALT_NEARBY_SWAP_ENTITY ^ desc1;  // FAST: leaf 0 = nearby change, leaf 1 = nearby swap
+            const uint64_t es0 = SALT_NEARBY_CHANGE_ENTITY ^ desc0(), es1 = SALT_NEARBY_SWAP_ENTITY ^ desc1();  // FAST: leaf 0 = nearby change, leaf 1 = nearby swap
             const uint64_t salt = lane == 0 ? SALT_UNION_OFFSET : lane == 1 ? es0 : lane == 2 ? (es0 ^ STRIDE_SALT_MIX) : lane == 3 ? es1 : (es1 ^ STRIDE_SALT_MIX);
             const FastMod fm2 = make_fastmod(2u);
             FastMod f;
@@ -971,6 +1031,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
             // the common case -- the next offset of the same entity inside the 64 offsets `pv` already holds -- is ONE compare: everything below
             // this test is the per-entity / per-chunk path (it used to be entered through two compound tests, ~20 scalar instructions per source)
             if (o >= c.cend) {
+            ISA_MARK("resolve_slow_begin");
             if (k != c.vk || o >= len) {  // a new entity: its list owner and length (skip empty routes; left > 0
                                           // guarantees a source exists)
                 for (;;) {
@@ -993,7 +1054,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                 // 64 consecutive offsets of this entity, one per lane: source position and source element, kept in a
                 // register (`pv` = position | element << 16); a source is then one v_readlane away, no LDS round trip
                 const uint64_t src_salt = ((l ? chg1 : chg0) ? SALT_NEARBY_CHANGE_SOURCE : SALT_NEARBY_SWAP_SOURCE) ^
-                                          (uint64_t)se ^ (l ? desc1 : desc0);
+                                          (uint64_t)se ^ (l ? desc1() : desc0());
                 const uint32_t oo = (o & ~63u) + lane;
                 const uint32_t spl = oo < len ? ctx.selection_index(oo, len, src_salt) : 0u;
                 const uint32_t sxl = oo < len ? (uint32_t)s_visits[s_off[se] + spl] : 0u;
@@ -1005,6 +1066,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
             c.k = k;
             c.se = se;
             c.len = len;
+            ISA_MARK("resolve_slow_end");
             }
             const uint32_t pvv = (uint32_t)__builtin_amdgcn_readlane((int)c.pv, (int)(o & 63u));
             const uint32_t sp = pvv & 0xFFFFu, sx = pvv >> 16;
@@ -1024,7 +1086,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
         LeafCursor C0{0, 0, total, 0, 0, 0, 0, 0, 0, 0xFFFFFFFFu, 0, 0, NBR_END, 0, 0};
         LeafCursor C1{0, 0, n_leaves > 1 ? total : 0u, 0, 0, 0, 0, 0, 0, 0xFFFFFFFFu, 0, n_leaves > 1 ? 0 : 1, NBR_END, 0, 0};
         for (int l = 0; l < n_leaves; ++l) {
-            const uint64_t ent_salt = ((l ? chg1 : chg0) ? SALT_NEARBY_CHANGE_ENTITY : SALT_NEARBY_SWAP_ENTITY) ^ (l ? desc1 : desc0);
+            const uint64_t ent_salt = ((l ? chg1 : chg0) ? SALT_NEARBY_CHANGE_ENTITY : SALT_NEARBY_SWAP_ENTITY) ^ (l ? desc1() : desc0());
             uint32_t pst, psd;
             if (lane_hash) {  // perm_params_fm with the two hashes already taken (above)
                 pst = (uint32_t)__builtin_amdgcn_readlane((int)hashed, l ? 3 : 1);
@@ -1076,10 +1138,12 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
             }
         }
         wave_sync();
+        if constexpr (SMALL) st_sources += C0.left + C1.left;  // sources generated this step = what leaves the two `left` counts: added here, the remainder taken off at the step's end (nothing to count in the fill loop; the general kernels count there)
         if (total > 0) {
             resolve(C0, 0);
             if (n_leaves > 1) resolve(C1, 1);
         }
+        ISA_MARK("prologue_end");
 
         PH(1)
         // ---- (C) candidate rounds: fill the rings, replay one 64-wide batch, repeat -----------
@@ -1185,6 +1249,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                 return emitted;
             };
             const uint32_t single0 = cv.rc - K0 < 64u ? cv.rc - K0 : 64u, single1 = cv.rc - K1 < 64u ? cv.rc - K1 : 64u;
+            ISA_MARK("fill_begin");
             for (;;) {
                 const bool both_live = !C0.ex && !C1.ex;
                 const bool need0 = !C0.ex && C0.left > 0 && C0.tail - C0.head < (both_live ? 32u : single0);
@@ -1205,7 +1270,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                     C1.left -= 1;
                     C1.o += 1;
                     if (C1.left > 0) resolve(C1, 1);
-                    st_sources += 2;
+                    if constexpr (!SMALL) st_sources += 2;
                     const uint32_t se = hi ? seB : seA, sp = hi ? spB : spA, len = hi ? lenB : lenA, kk = hi ? kB : kA;
                     const uint32_t Kh = hi ? K1 : K0;
                     const bool have = key != NBR_END;
@@ -1318,7 +1383,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                     c.left -= 1;
                     c.o += 1;
                     if (c.left > 0) resolve(c, l);
-                    st_sources += 1;
+                    if constexpr (!SMALL) st_sources += 1;
                     c.tail += gen_rest(l, se, sp, len, k, sx, c.tail, key, 0u, l ? K1 : K0, 0u);
                     if (l)
                         C1 = c;
@@ -1326,6 +1391,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                         C0 = c;
                 }
             }
+            ISA_MARK("fill_end");
             wave_sync();
             PH(2)
 
@@ -1337,8 +1403,9 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                     done = 1;
                     break;
                 }
+                const bool both = live0 && live1;
                 uint32_t lf, idx;
-                if (live0 && live1) {
+                if (both) {
                     const uint32_t l0 = (first_leaf + pulls) & 1u;
                     lf = (l0 + lane) & 1u;
                     idx = (lf ? C1.head : C0.head) + (lane >> 1);
@@ -1381,7 +1448,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                         m0 = rq[0];
                         m1 = rq[1];
                         const uint32_t a = m0 >> 16, i = m0 & 0xFFFFu, b = m1 >> 16, j = m1 & 0xFFFFu;
-                        eval_generated_small<L, LT, COMPACT, OT>(m, s_visits, s_off, s_load, 1u - lfq, a, i, b, j, dv);  // FAST: leaf 0 = change, leaf 1 = swap; COMPACT reads the u16 matrix
+                        eval_generated_small<L, LT, COMPACT, OT>(m, lvl, s_visits, s_off, s_load, 1u - lfq, a, i, b, j, dv);  // FAST: leaf 0 = change, leaf 1 = swap; COMPACT reads the u16 matrix
                     }
                     doable = valid;
                     // LateAcceptance: score >= last step score || score >= late score (late_acceptance.rs:89-125).  Two levels: the pair of int32 deltas
@@ -1418,13 +1485,23 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                             M[kk] = wave_max_i32(in_max ? dv[kk] : (int32_t)0x80000000);
                             in_max = in_max && dv[kk] == M[kk];
                         }
-                        const bool ge = !has_best || small_ge<L>(M, best_d);
+                        // (two levels: the forager's best is best_key alone -- best_d[] would be the same value a second time in two more registers)
+                        int64_t Mkey = 0;
+                        if constexpr (L == 2) Mkey = (int64_t)(((uint64_t)(uint32_t)M[0] << 32) + (uint64_t)(int64_t)M[1]);
+                        bool ge, gt;
+                        if constexpr (L == 2) {
+                            ge = !has_best || Mkey >= best_key;
+                            gt = !has_best || Mkey > best_key;
+                        } else {
+                            ge = !has_best || small_ge<L>(M, best_d);
+                            gt = !has_best || !small_ge<L>(best_d, M);
+                        }
                         if (ge) {
-                            const bool newmax = !has_best || !small_ge<L>(best_d, M);
-                            const uint64_t eq_base = newmax ? 0 : equal_count;
+                            const bool newmax = gt;
+                            const uint32_t eq_base = newmax ? 0u : equal_count;
                             const uint64_t eq = __ballot(in_max);
                             const uint32_t rank = mbcnt64(eq) + 1u;
-                            const uint64_t cntq = eq_base + rank;
+                            const uint64_t cntq = (uint64_t)(eq_base + rank);
                             const bool pick = in_max && ((newmax && rank == 1) ||
                                                          (p.random_ties && cntq > 1 && reservoir_pick(sseed, cntq)));
                             const uint64_t pm = __ballot(pick);
@@ -1434,10 +1511,13 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                                 best_m1 = __shfl(m1, sel);
                                 best_leaf = (int)__shfl(lf, sel);
                             }
+                            if constexpr (L == 2) {
+                                best_key = Mkey;
+                            } else {
 #pragma unroll
-                            for (int kk = 0; kk < L; ++kk) best_d[kk] = M[kk];
-                            if constexpr (L == 2) best_key = (int64_t)(((uint64_t)(uint32_t)M[0] << 32) + (uint64_t)(int64_t)M[1]);
-                            equal_count = eq_base + (uint64_t)__popcll(eq);
+                                for (int kk = 0; kk < L; ++kk) best_d[kk] = M[kk];
+                            }
+                            equal_count = eq_base + (uint32_t)__popcll(eq);
                             has_best = 1;
                         }
                     }
@@ -1556,7 +1636,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                 uint32_t c1;
                 if constexpr (SMALL) {  // the lanes alternate the two leaves from the batch's first pull on: no ballot needed
                     const uint32_t lfirst = (uint32_t)__builtin_amdgcn_readfirstlane((int)lf);
-                    c1 = (live0 && live1) ? ((nconsumed + lfirst) >> 1) : (lfirst ? nconsumed : 0u);
+                    c1 = both ? ((nconsumed + lfirst) >> 1) : (lfirst ? nconsumed : 0u);
                 } else {
                     c1 = (uint32_t)__popcll(__ballot(consumed && lf == 1u));
                 }
@@ -1571,7 +1651,14 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
         PH(4)
 
         // ---- (D) commit the forager's pick (step.rs:122-221) ----------------------------------
+        ISA_MARK("commit_begin");
+        if constexpr (SMALL) st_sources -= C0.left + C1.left;
         if constexpr (SMALL) {
+            if constexpr (L == 2) {  // the key back into its two level deltas, once per step: key = hard x 2^32 + soft (sign-extended)
+                const int32_t soft = (int32_t)(uint32_t)(uint64_t)best_key;
+                best_d[1] = soft;
+                best_d[0] = (int32_t)(uint32_t)((uint64_t)wsub(best_key, (int64_t)soft) >> 32);
+            }
 #pragma unroll
             for (int kk = 0; kk < L; ++kk) best.v[kk] = wadd(cur[kk], (int64_t)best_d[kk]);
         }
@@ -1583,8 +1670,10 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                 for (int kk = 0; kk < L; ++kk) bs.v[kk] = best_sol[kk];
                 if (!(score_cmp<L>(best, bs) > 0)) {  // leaving the best state: write its snapshot first
                     const uint32_t tot = uni(s_off[V]);
-                    for (uint32_t t = lane; t < tot; t += 64) m.best_visits[(size_t)r * m.n_cap + t] = ext_id(s_visits[t]);
-                    for (uint32_t t = lane; t <= (uint32_t)V; t += 64) m.best_off[(size_t)r * (V + 1) + t] = s_off[t];
+                    uint32_t* const bv = SF_COLD_M(best_visits) + (size_t)r * SF_COLD_M(n_cap);
+                    uint32_t* const bo = SF_COLD_M(best_off) + (size_t)r * (V + 1);
+                    for (uint32_t t = lane; t < tot; t += 64) bv[t] = ext_id(s_visits[t]);
+                    for (uint32_t t = lane; t <= (uint32_t)V; t += 64) bo[t] = s_off[t];
                     best_pending = false;
                 }
             }
@@ -1637,9 +1726,11 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                 for (int kk = 0; kk < L; ++kk) best_sol[kk] = cur[kk];
             }
             // acceptor.step_ended(last_step_score) always (step.rs:216-221)
+            const int la_size = SF_COLD_P(la_size);
             if ((acceptor == 1 || acceptor == 4) && lane == 0) {
+                int64_t* const lh = SF_COLD_P(la_hist) + ((size_t)r * la_size + la_slot) * 4;
 #pragma unroll
-                for (int kk = 0; kk < L; ++kk) p.la_hist[((size_t)r * p.la_size + la_slot) * 4 + kk] = cur[kk];
+                for (int kk = 0; kk < L; ++kk) lh[kk] = cur[kk];
             }
             if (acceptor == 4 && lane == 0) {  // step_ended: the phase's best step score (diversified_late_acceptance.rs:161-170)
                 ScoreV<L> cs, db;
@@ -1662,10 +1753,15 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                 st_calc += pulls;
                 st_acc += accepted;
             }
-            la_cursor = la_cursor + 1 >= p.la_size ? 0 : la_cursor + 1;
-            if (p.move_budget > 0 && (int64_t)st_gen >= p.move_budget) break;  // work-balanced launch: see sf_solve_moves (budget < 2^31)
-            if (p.move_budget == 0 && st_scored >= 0x70000000u) flush_stats();
+            la_cursor = la_cursor + 1 >= la_size ? 0 : la_cursor + 1;
+            const int64_t move_budget = SF_COLD_P(move_budget);
+            if (move_budget > 0 && (int64_t)st_gen >= move_budget) {  // work-balanced launch: see sf_solve_moves (budget < 2^31)
+                if constexpr (SMALL) ++step;
+                break;
+            }
+            if (move_budget == 0 && st_scored >= 0x70000000u) flush_stats();
         }
+        ISA_MARK("commit_end");
         PH(5)
     }
     PH_DUMP
@@ -1675,27 +1771,47 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
         if constexpr (!FAST)
             if (annealing) sa_store(saw, p.sa, r, lane);
         const uint32_t tot = uni(s_off[V]);
+        // SMALL: the replica's base pointers, formed again from the argument block
+        const size_t n_cap = (size_t)SF_COLD_M(n_cap);
+        uint32_t* const w_visits = SMALL ? SF_COLD_M(visits) + (size_t)r * n_cap : g_visits;
+        uint32_t* const w_off = SMALL ? SF_COLD_M(off) + (size_t)r * (V + 1) : g_off;
+        int64_t* const w_load = SMALL ? SF_COLD_M(load) + (size_t)r * V : g_load;
+        int64_t* const w_score = SMALL ? SF_COLD_M(score) + (size_t)r * 4 : g_score;
         if (best_pending) {  // the launch ends in a best state: its deferred snapshot
-            for (uint32_t t = lane; t < tot; t += 64) m.best_visits[(size_t)r * m.n_cap + t] = ext_id(s_visits[t]);
-            for (uint32_t t = lane; t <= (uint32_t)V; t += 64) m.best_off[(size_t)r * (V + 1) + t] = s_off[t];
+            uint32_t* const bv = SF_COLD_M(best_visits) + (size_t)r * n_cap;
+            uint32_t* const bo = SF_COLD_M(best_off) + (size_t)r * (V + 1);
+            for (uint32_t t = lane; t < tot; t += 64) bv[t] = ext_id(s_visits[t]);
+            for (uint32_t t = lane; t <= (uint32_t)V; t += 64) bo[t] = s_off[t];
         }
-        for (uint32_t t = lane; t < tot; t += 64) g_visits[t] = ext_id(s_visits[t]);
-        for (uint32_t t = lane; t <= (uint32_t)V; t += 64) g_off[t] = s_off[t];
-        for (uint32_t t = lane; t < (uint32_t)V; t += 64) g_load[t] = (int64_t)s_load[t];
+        for (uint32_t t = lane; t < tot; t += 64) w_visits[t] = ext_id(s_visits[t]);
+        for (uint32_t t = lane; t <= (uint32_t)V; t += 64) w_off[t] = s_off[t];
+        for (uint32_t t = lane; t < (uint32_t)V; t += 64) w_load[t] = (int64_t)s_load[t];
         if (lane == 0) {
 #pragma unroll
             for (int kk = 0; kk < L; ++kk) {
-                g_score[kk] = cur[kk];
-                p.last_step_score[(size_t)r * 4 + kk] = cur[kk];
-                m.best_score[(size_t)r * 4 + kk] = best_sol[kk];
+                w_score[kk] = cur[kk];
+                SF_COLD_P(last_step_score)[(size_t)r * 4 + kk] = cur[kk];
+                SF_COLD_M(best_score)[(size_t)r * 4 + kk] = best_sol[kk];
             }
-            p.la_idx[r] = la_cursor;
-            p.step_index[r] = step_index0 + steps_run + (uint64_t)st_steps;  // steps actually run (a move budget can end the launch early)
-            p.seed_draws[r] = seed_draws0 + steps_run + (uint64_t)st_steps;
+            SF_COLD_P(la_idx)[r] = la_cursor;
+            const uint64_t ran = SMALL ? (uint64_t)step : steps_run + (uint64_t)st_steps;  // steps actually run
+            SF_COLD_P(step_index)[r] = step_index0 + ran;
+            SF_COLD_P(seed_draws)[r] = seed_draws0 + ran;
         }
         flush_stats();
     }
     if (tracing && lane == 0) *p.trace_count = (int64_t)trace_n;
 }
+
+#undef SF_COLD_P
+#undef SF_COLD_M
+
+// cold_args(): the kernel's parameter list is WaveArgs' member list (one signature for every instantiation)
+template <class F>
+struct wave_args_are : std::false_type {};
+template <>
+struct wave_args_are<void (*)(decltype(WaveArgs::m), decltype(WaveArgs::p), decltype(WaveArgs::nb))> : std::true_type {};
+static_assert(wave_args_are<decltype(&k_list_search_wave<2, false, 2>)>::value && std::is_standard_layout<WaveArgs>::value,
+              "WaveArgs must list k_list_search_wave's parameters, in order: cold_args() reads the kernarg segment through it");
 
 }  // namespace sf
