@@ -10,6 +10,11 @@ the text); resolve()'s slow path is inlined several times and is one row.
   spill VGPR   a VGPR that appears only as the destination of v_writelane or the source of v_readlane
   step loop    the backward branch with the largest span
   const/carried  a reload of a slot (register, lane) written only before the step loop / written inside it
+  vector-memory waits   per region, the vector-memory loads and the s_waitcnt that name vmcnt, as "n x vmcnt(k)" -- here an instruction counts in
+                 its INNERMOST region only, so `pair` is the paired pass without resolve()'s slow path (resolve_slow) and without the gen_rest
+                 continuation (pair_rest): its common path.  A load that stays in flight across the pass shows as `pair` with loads and no wait;
+                 the one wait for the loads of the pass before is scheduled in front of the pair_begin mark and counts in `fill`.  The last column
+                 is the text order of the two (L a load, w a wait), which is not the order of execution.
 Opcodes are classified by prefix (scripts/isa_blocks.py: cat)."""
 import os
 import re
@@ -158,10 +163,19 @@ def report(path, needle, out=sys.stdout):
             names.append("step loop, all")
         for n in names:
             if n not in rows:
-                rows[n] = dict(rc=0, rk=0, st=0, nop=0, ws=0, salu=0, valu=0, lds=0, vmem=0, n=0)
+                rows[n] = dict(rc=0, rk=0, st=0, nop=0, ws=0, salu=0, valu=0, lds=0, vmem=0, n=0, vmw={}, vml=0, seq="")
                 order.append(n)
             row = rows[n]
             row["n"] += 1
+            if not st or n == st[-1]:  # the vector-memory columns: innermost region only
+                if op == "s_waitcnt":
+                    m = re.search(r"vmcnt\((\d+)\)", " ".join(ops))
+                    if m:
+                        row["vmw"][int(m.group(1))] = row["vmw"].get(int(m.group(1)), 0) + 1
+                        row["seq"] += "w"
+                elif op.startswith(("global_load", "buffer_load", "flat_load")):
+                    row["vml"] += 1
+                    row["seq"] += "L"
             if op.startswith("v_readlane") and vregs(ops[1])[0] in spill:
                 row["rk" if (vregs(ops[1])[0], ops[2]) in written_in else "rc"] += 1
             elif op.startswith("v_writelane") and vregs(ops[0])[0] in spill:
@@ -189,6 +203,12 @@ def report(path, needle, out=sys.stdout):
         row = rows[n]
         p("  %-47s %6d | %7d %8d %8d | %6d %10d | %6d %6d %6d %6d %5d" % (n, row["n"], row["rc"] + row["rk"], row["rc"], row["rk"], row["st"], row["rc"] + row["rk"] + row["st"],
                                                                    row["nop"], row["ws"], row["salu"], row["valu"], row["lds"] + row["vmem"]))
+    p("  vector-memory loads and waits, each in its innermost region (last column: text order, L a load, w a wait that names vmcnt)")
+    for n in sorted(order, key=lambda n: (n.startswith("("), n == "step loop, all", n)):
+        row = rows[n]
+        if n == "step loop, all" or n.startswith("("):
+            continue
+        p("  %-47s loads %3d | waits %s | %s" % (n, row["vml"], " ".join("%d x vmcnt(%d)" % (c, k) for k, c in sorted(row["vmw"].items())) or "none", row["seq"]))
     p("")
 
 

@@ -136,6 +136,10 @@ struct NodeSlotT<false> {
     __device__ __forceinline__ void clear(uint32_t node) const { p[node] = NODE_NONE; }
     __device__ __forceinline__ void set(uint32_t node, uint32_t route, uint32_t pos) const { p[node] = (route << 16) | pos; }
     __device__ __forceinline__ uint32_t get(uint32_t node) const { return p[node]; }
+    // the table word, and its wide form (the same thing in this layout): see NodeSlotT<true>
+    __device__ __forceinline__ uint32_t word(uint32_t node) const { return p[node]; }
+    __device__ __forceinline__ uint32_t wide(uint32_t s, uint32_t) const { return s; }
+    __device__ __forceinline__ uint32_t wide_short(uint32_t s) const { return s; }
 };
 template <>
 struct NodeSlotT<true> {
@@ -156,8 +160,11 @@ struct NodeSlotT<true> {
     __device__ __forceinline__ void set(uint32_t node, uint32_t route, uint32_t pos) const {
         p[node] = (uint16_t)((route << pb) | (pos < pmax ? pos : pmax));
     }
-    __device__ __forceinline__ uint32_t get(uint32_t node) const {
-        const uint32_t s = p[node];
+    __device__ __forceinline__ uint32_t get(uint32_t node) const { return wide(p[node], node); }
+    // get() in two halves, for a caller that wants the LDS read in flight while it does something else: word() is the read, wide() / wide_short()
+    // turn the word into (route << 16 | position)
+    __device__ __forceinline__ uint32_t word(uint32_t node) const { return p[node]; }
+    __device__ __forceinline__ uint32_t wide(uint32_t s, uint32_t node) const {
         const bool none = s == 0xFFFFu;
         const uint32_t route = s >> pb;
         uint32_t pos = s & pmax;
@@ -170,6 +177,11 @@ struct NodeSlotT<true> {
             }
         }
         return none ? NODE_NONE : ((route << 16) | pos);
+    }
+    // wide() for a caller that KNOWS no route is longer than pmax (no position is stored saturated): the word decoded, nothing tested
+    __device__ __forceinline__ uint32_t wide_short(uint32_t s) const {
+        const uint32_t w = ((s >> pb) << 16) | (s & pmax);
+        return s == 0xFFFFu ? NODE_NONE : w;
     }
 };
 // does the compact layout carry this model?  route ids need a bit pattern below all-ones, positions at least 6 bits
@@ -242,6 +254,13 @@ struct RouteArith {
     }
     __device__ __forceinline__ static uint32_t rank(uint32_t w) { return w; }
     __device__ __forceinline__ static uint32_t inter_ord(uint32_t w, uint32_t dp) { return ORD_ARITH_BASE + (w << 16) + dp; }
+};
+struct RouteRank {  // RouteTab's table holding the rank alone, RouteArith's ordinals
+    const uint32_t* rt;
+    static constexpr int KEY_SHIFT = RouteArith::KEY_SHIFT;
+    __device__ __forceinline__ uint32_t word(uint32_t route) const { return rt[route]; }
+    __device__ __forceinline__ static uint32_t rank(uint32_t w) { return w; }
+    __device__ __forceinline__ static uint32_t inter_ord(uint32_t w, uint32_t dp) { return RouteArith::inter_ord(w, dp); }
 };
 template <class OT, class RT>
 __device__ __forceinline__ NearbyItem nearby_item_rt(bool is_change, uint32_t slot, uint32_t se, uint32_t sp,
@@ -797,6 +816,12 @@ __device__ __forceinline__ ColdArgs cold_args() {
 template <int L, bool TRACE, int MODE, bool COMPACT = false, int WPE = SF_WAVES_PER_EU, bool NODEG = false>
 __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m, SearchParams p, NbrIndex nb) {
     constexpr bool FAST = MODE >= 1, SMALL = MODE == 2;
+    // LEAN: the FAST + SMALL kernels -- the ones whose bound is the scalar unit -- have the paired pass of DESIGN 17: row entries and the node-table
+    // read in flight across resolve(), half selects as words, a branch-free item, closed groups in lanes; SAT (their COMPACT layouts): the table's
+    // saturation scan behind a count; RANKTAB (the COMPACT layouts that keep a route table): the table holds the rank alone.  The general kernels
+    // compile the pass they had.  (How each of the five was built and measured on its own: profiles/wave_pair_levers.txt.)
+    constexpr bool LEAN = FAST && SMALL;
+    constexpr bool SAT = LEAN && COMPACT, RANKTAB = LEAN && COMPACT && !NODEG;
 // A cold field of `p` / `m`: the FAST + SMALL kernels -- the ones whose bound is the scalar unit -- read it from the argument block where it
 // is used, the others from the by-value structs.  (Local to this kernel: the macros name its `SMALL`, `p` and `m`, and end with it.)
 #define SF_COLD_P(f) (SMALL ? cold_args()->p.f : p.f)
@@ -857,7 +882,9 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
     // 322 -> 227 B of memory-side traffic per candidate without it.  With the table in LDS (CVRP-1000) the lookup is cheaper than the arithmetic
     // (50.4 -> 48.8 G when every COMPACT kernel computed ranks, profiles/r06d_route_arith_ab.txt), so those keep it.
     constexpr bool ARANK = NODEG;
-    using RT = typename std::conditional<ARANK, RouteArith, RouteTab>::type;
+    // RANKTAB: the table holds the rank alone and the inter-list ordinal is (rank << 16 | position), as in
+    // RouteArith -- it is only ever compared inside one equal-distance group -- so the prologue needs no prefix scan over the lists
+    using RT = typename std::conditional<ARANK, RouteArith, typename std::conditional<RANKTAB, RouteRank, RouteTab>::type>::type;
     uint32_t* rtab = (uint32_t*)(mem + cv.rtab);
     uint16_t* route_at = (uint16_t*)(mem + cv.routeat);  // [leaf][rank] -> route
 
@@ -887,6 +914,16 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
     }
     node_sync();
 
+    // SAT: the number of routes longer than pmax, i.e. with positions stored saturated in the 16-bit table (wave-uniform; kept at the commit).
+    // While it is zero the paired pass decodes the table word with wide_short(): no ballot, no region, nothing waits for the read on the spot.
+    uint32_t nsat = 0;
+    if constexpr (SAT) {
+        for (uint32_t base = 0; base < (uint32_t)V; base += 64) {
+            const uint32_t v = base + lane;
+            const bool lg = v < (uint32_t)V && (uint32_t)(s_off[v + 1] - s_off[v]) > node_slot.pmax;
+            nsat += (uint32_t)__popcll(__ballot(lg));
+        }
+    }
     auto ext_id = [&](uint32_t x) -> uint32_t { return (COMPACT && m.inv) ? (uint32_t)m.inv[x] : x; };  // an LDS element under the caller's numbering
     int64_t cur[L], best_sol[L];
 #pragma unroll
@@ -920,6 +957,16 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
     const int la_idx0 = dry_run ? 0 : p.la_idx[r];
     int la_cursor = la_idx0;  // (la_idx0 + step) % la_size, kept incrementally (no 64-bit division per step)
     const uint64_t lanebit = 1ULL << lane;
+    // LEAN kernels: the paired pass picks a half's facts with a per-lane WORD, not with the 64-bit mask `lane >= 32`: `hm` is all-ones in lanes
+    // 32-63 and zero in lanes 0-31, and half(a, b) = a in the lower half, b in the upper one, is a v_and and a v_and_or.  The mask lived in spill
+    // lanes and was read back five times per pass; a word select needs no scalar register at all.  (The empty asm keeps it a word: left to itself
+    // the compiler turns it back into the compare.)
+    uint32_t hm = 0;  // (LEAN kernels only)
+    if constexpr (LEAN) {
+        hm = (uint32_t)((int32_t)(lane << 26) >> 31);
+        asm volatile("" : "+v"(hm));
+    }
+    auto half = [&](uint32_t lo, uint32_t up) -> uint32_t { return (lo & ~hm) | (up & hm); };
     PH_DECL
 
     const LevelWords<L> lvl = level_words<L, SMALL>(m);
@@ -1022,7 +1069,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
             if constexpr (ARANK)
                 return RouteArith{l ? perm_st1 : perm_st0, l ? perm_inv1 : perm_inv0, (uint32_t)V, v_recip32};
             else
-                return RouteTab{rtab + l * V};
+                return RT{rtab + l * V};
         };
         // resolve the source at cursor (k, o) of leaf l and put its first key chunk in flight
         auto resolve = [&](LeafCursor& c, int l) {
@@ -1078,8 +1125,15 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
             // unconditional load (a lane past a row shorter than 64 entries reads the row's last entry and is then blanked): no exec-mask region
             const uint32_t entc = ent < dim ? ent : dim - 1u;
             const uint32_t pk_any = (uint32_t) * (const uint16_t*)((const char*)nb.keys + ((sx * dim + entc) << 1));
-            c.pk = ent < dim ? pk_any : NBR_END;
+            // LEAN: the entry stays raw -- blanking it here consumes the load on the spot (a full wait for the row right behind its issue);
+            // whoever takes the key blanks the lanes past the row (row_key), one pass later, and the load is in flight until then
+            if constexpr (LEAN)
+                c.pk = pk_any;
+            else
+                c.pk = ent < dim ? pk_any : NBR_END;
         };
+        // the key of row entry `e` out of a raw prefetched entry
+        auto row_key = [&](uint32_t raw, uint32_t e) -> uint32_t { return LEAN ? (e < dim ? raw : NBR_END) : raw; };
 
         PH(0)
         // ---- (B) per-leaf entity order tables (slot.rs:468-499) --------------------------------
@@ -1123,18 +1177,22 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
             }
             uint16_t* ra = route_at + l * V;
             uint32_t* rt = rtab + l * V;
-            uint32_t carry = 0;  // first slot ordinal of rank k = sum_{k'<k} (len(route_at[k']) + 1)
+            [[maybe_unused]] uint32_t carry = 0;  // (not RANKTAB) first slot ordinal of rank k = sum_{k'<k} (len(route_at[k']) + 1)
             for (uint32_t base = 0; base < (uint32_t)V; base += 64) {
                 const uint32_t k = base + lane;
-                uint32_t v = 0, e = 0;
-                if (k < (uint32_t)V) {
-                    e = fastmod_u64((uint64_t)pst + (uint64_t)k * psd, fm_V);
-                    if constexpr (!COMPACT) ra[k] = (uint16_t)e;
-                    v = s_off[e + 1] - s_off[e] + 1;
+                if constexpr (RANKTAB) {  // the rank alone: no list lengths, no prefix scan
+                    if (k < (uint32_t)V) rt[fastmod_u64((uint64_t)pst + (uint64_t)k * psd, fm_V)] = k;
+                } else {
+                    uint32_t v = 0, e = 0;
+                    if (k < (uint32_t)V) {
+                        e = fastmod_u64((uint64_t)pst + (uint64_t)k * psd, fm_V);
+                        if constexpr (!COMPACT) ra[k] = (uint16_t)e;
+                        v = s_off[e + 1] - s_off[e] + 1;
+                    }
+                    const uint32_t inc = wave_incl_scan(v);
+                    if (k < (uint32_t)V) rt[e] = k | ((carry + inc - v) << 16);
+                    carry += __shfl(inc, 63);
                 }
-                const uint32_t inc = wave_incl_scan(v);
-                if (k < (uint32_t)V) rt[e] = k | ((carry + inc - v) << 16);
-                carry += __shfl(inc, 63);
             }
         }
         wave_sync();
@@ -1248,6 +1306,17 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                 }
                 return emitted;
             };
+            // the paired pass's table word into (route << 16 | position).  SAT: the short form, the saturation scan only while some route is longer than
+            // pmax -- the common path is one scalar compare (on the count itself: the asm keeps the compiler from carrying `nsat != 0` as a lane mask)
+            auto slot_of = [&](uint32_t word, uint32_t node) -> uint32_t {
+                if constexpr (SAT) {
+                    uint32_t ns = nsat;
+                    asm volatile("" : "+s"(ns));
+                    if (ns != 0) return node_slot.wide(word, node);
+                    return node_slot.wide_short(word);
+                } else
+                    return node_slot.wide(word, node);
+            };
             const uint32_t single0 = cv.rc - K0 < 64u ? cv.rc - K0 : 64u, single1 = cv.rc - K1 < 64u ? cv.rc - K1 : 64u;
             ISA_MARK("fill_begin");
             for (;;) {
@@ -1263,7 +1332,19 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                     const bool hi = lane >= 32;
                     const uint32_t seA = C0.se, spA = C0.sp, lenA = C0.len, kA = C0.k, sxA = C0.sx, tlA = C0.tail;
                     const uint32_t seB = C1.se, spB = C1.sp, lenB = C1.len, kB = C1.k, sxB = C1.sx, tlB = C1.tail;
-                    const uint32_t key = hi ? C1.pk : C0.pk;
+                    // LEAN: each half blanks the lanes past its row now (resolve() left the entries raw)
+                    uint32_t l31 = lane & 31u;
+                    if constexpr (LEAN) asm volatile("" : "+v"(l31));  // (formed per pass: hoisted out of the loops, `l31 < dim` is a 64-bit mask in spill lanes)
+                    const uint32_t key = LEAN ? row_key(half(C0.pk, C1.pk), l31) : (hi ? C1.pk : C0.pk);
+                    const bool have = key != NBR_END;
+                    uint32_t nd = have ? (key & NBR_NODE_MASK) : 0u;  // unconditional read below (node 0 for the lanes past the row)
+                    uint32_t slot_word = 0;
+                    if constexpr (LEAN) {
+                        // the current keys are taken HERE, before the next sources' row loads issue: the only wait for a row load in the pass is this one,
+                        // for the loads of the pass before (the asm pins the order: the scheduler would otherwise sink the use below the new loads)
+                        asm volatile("" : "+v"(nd)::"memory");
+                        slot_word = node_slot.word(nd);  // ... and the table read is in flight across resolve()
+                    }
                     C0.left -= 1;
                     C0.o += 1;
                     if (C0.left > 0) resolve(C0, 0);
@@ -1271,18 +1352,64 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                     C1.o += 1;
                     if (C1.left > 0) resolve(C1, 1);
                     if constexpr (!SMALL) st_sources += 2;
-                    const uint32_t se = hi ? seB : seA, sp = hi ? spB : spA, len = hi ? lenB : lenA, kk = hi ? kB : kA;
-                    const uint32_t Kh = hi ? K1 : K0;
-                    const bool have = key != NBR_END;
+                    uint32_t slot_any;
+                    if constexpr (LEAN)
+                        slot_any = slot_of(slot_word, nd);
+                    else
+                        slot_any = node_slot.get(nd);
+                    const uint32_t slot = have ? slot_any : NODE_NONE;
                     NearbyItem it{0u, 0u, 0u, 0u};
-                    {
-                        const uint32_t slot_any = node_slot.get(have ? (key & NBR_NODE_MASK) : 0u);  // unconditional read (node 0 for the lanes past the row)
-                        const uint32_t slot = have ? slot_any : NODE_NONE;
+                    uint32_t mv0, tl, Kh, rq_off;  // this lane's half: source (entity << 16 | position), ring tail, max_nearby, ring offset in words
+                    if constexpr (LEAN) {
+                        // leaf 0 = nearby change (lanes 0-31), leaf 1 = nearby swap (lanes 32-63), as in the FAST item below, but every fact of a half picked
+                        // with half() and every predicate ONE unsigned compare of two selected words: no `hi` mask, no nested exec-mask regions.
+                        //   v0  change: another list, or dp - sp >= 2 (unsigned)     swap: intra dp > sp, inter rank > k
+                        //       as x > y with   intra: x = dp - (change ? sp : 0), y = change ? 1 : sp     inter: x = change ? ~0 : rank, y = change ? 0 : k
+                        //   v1  change only: dp + 1 == len2 and (another list or len != sp + 1), as one word that is zero exactly then
+                        const uint32_t sev = half(seA, seB), spv = half(spA, spB);
+                        mv0 = (sev << 16) | spv;
+                        tl = half(tlA, tlB);
+                        Kh = half(K0, K1);
+                        rq_off = hm & (cv.rc * 2u);
+                        // (every arm of a select below is a value already computed: a `?:` with work in an arm is compiled as an exec-mask region)
+                        const bool some = slot != NODE_NONE;
+                        const uint32_t r_any = slot >> 16, dp = slot & 0xFFFFu;
+                        const uint32_t r2 = some ? r_any : 0u;
+                        const uint32_t len2 = s_off[r2 + 1] - s_off[r2];
+                        uint32_t t;
+                        if constexpr (ARANK)
+                            t = RouteArith{half(perm_st0, perm_st1), half(perm_inv0, perm_inv1), (uint32_t)V, v_recip32}.word(r2);
+                        else
+                            t = rtab[r2 + (hm & (uint32_t)V)];
+                        const bool intra = r2 == sev;
+                        const uint32_t end_pay = (r2 << 16) | len2;
+                        const uint32_t xi = dp - (spv & ~hm), yi = half(1u, spv);
+                        const uint32_t xo = RT::rank(t) | ~hm, yo = kB & hm;
+                        const uint32_t xs = intra ? xi : xo, ys = intra ? yi : yo;
+                        const bool v0 = xs > ys;
+                        const uint32_t last = lenA ^ (spv + 1u);  // zero: the source is the last element of its list
+                        const uint32_t f = intra ? last : 1u;
+                        const uint32_t z1 = (((dp + 1u) ^ len2) | hm) | (1u - min(f, 1u));
+                        const bool v1 = z1 == 0u;
+                        const uint32_t b0 = v0 ? 1u : 0u, b1 = v1 ? 1u : 0u;
+                        const uint32_t wsum = b0 + b1;
+                        it.w = some ? wsum : 0u;
+                        const uint32_t len_or_dp = half(lenA, dp), ord_intra = v0 ? dp : len_or_dp, ord_inter = RT::inter_ord(t, dp);
+                        it.ord = intra ? ord_intra : ord_inter;
+                        const uint32_t end_or_slot = half(end_pay, slot);
+                        it.pay0 = v0 ? slot : end_or_slot;
+                        it.pay1 = end_pay;
+                    } else {
+                        const uint32_t se = hi ? seB : seA, sp = hi ? spB : spA, len = hi ? lenB : lenA, kk = hi ? kB : kA;
+                        mv0 = (se << 16) | sp;
+                        tl = hi ? tlB : tlA;
+                        Kh = hi ? K1 : K0;
+                        rq_off = hi ? cv.rc * 2u : 0u;
                         RT rth;
                         if constexpr (ARANK)
                             rth = RouteArith{hi ? perm_st1 : perm_st0, hi ? perm_inv1 : perm_inv0, (uint32_t)V, v_recip32};
                         else
-                            rth = RouteTab{rtab + (hi ? V : 0)};
+                            rth = RT{rtab + (hi ? V : 0)};
                         if constexpr (FAST) {
                             // leaf 0 = nearby change (lanes 0-31), leaf 1 = nearby swap (lanes 32-63): the two items of nearby_item_rt written as ONE, the
                             // facts they share read once and the half a lane belongs to folded into the predicates (nearby_change.rs:133-195, nearby_swap.rs)
@@ -1311,16 +1438,31 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                         }
                     }
                     const uint64_t havemask = __ballot(have);
-                    const uint64_t startmask = __ballot(have && ((lane & 31u) == 0 || !(key & NBR_SAME_FLAG)));
+                    // a group starts at the half's first lane and wherever the entry does not continue the previous one's distance.  LEAN: one compare,
+                    // key < 0x8000 (no NBR_SAME_FLAG, not NBR_END) in general and key < NBR_END at the half's first lane
+                    const uint64_t startmask = LEAN ? __ballot(key < NBR_END - min(l31, 1u) * (NBR_END - NBR_SAME_FLAG))
+                                                        : __ballot(have && (l31 == 0 || !(key & NBR_SAME_FLAG)));
                     const uint32_t hvA = (uint32_t)havemask, hvB = (uint32_t)(havemask >> 32);
                     const uint32_t stA = (uint32_t)startmask, stB = (uint32_t)(startmask >> 32);
                     const bool moreA = hvA == 0xFFFFFFFFu && 32u < dim, moreB = hvB == 0xFFFFFFFFu && 32u < dim;
                     // complete groups of each half (a half whose only group is still open contributes nothing)
-                    const uint32_t ncA = moreA ? 31u - (uint32_t)__clz(stA) : (uint32_t)__popc(hvA);
-                    const uint32_t ncB = moreB ? 31u - (uint32_t)__clz(stB) : (uint32_t)__popc(hvB);
-                    const uint64_t closedmask = (uint64_t)(ncA >= 32 ? 0xFFFFFFFFu : ((1u << ncA) - 1u)) |
-                                                ((uint64_t)(ncB >= 32 ? 0xFFFFFFFFu : ((1u << ncB) - 1u)) << 32);
-                    const bool closed = (closedmask & lanebit) != 0;
+                    uint32_t ncA = 0, ncB = 0;
+                    uint64_t closedmask;
+                    bool closed;
+                    if constexpr (LEAN) {
+                        // every lane works its own half's count out of its half's two words (vector instructions; the scalar form was ~30 instructions of
+                        // s_flbit / s_bcnt1 / s_cselect / s_lshl per pass) -- the compare IS the closed mask; ncA / ncB are formed only where gen_rest is called
+                        const uint32_t hvv = half(hvA, hvB), stv = half(stA, stB);
+                        const uint32_t ncv = (hvv == 0xFFFFFFFFu && 32u < dim) ? 31u - (uint32_t)__clz(stv) : (uint32_t)__popc(hvv);
+                        closed = l31 < ncv;
+                        closedmask = __ballot(closed);
+                    } else {
+                        ncA = moreA ? 31u - (uint32_t)__clz(stA) : (uint32_t)__popc(hvA);
+                        ncB = moreB ? 31u - (uint32_t)__clz(stB) : (uint32_t)__popc(hvB);
+                        closedmask = (uint64_t)(ncA >= 32 ? 0xFFFFFFFFu : ((1u << ncA) - 1u)) |
+                                     ((uint64_t)(ncB >= 32 ? 0xFFFFFFFFu : ((1u << ncB) - 1u)) << 32);
+                        closed = (closedmask & lanebit) != 0;
+                    }
                     const uint32_t wc = closed ? it.w : 0u;
                     const uint64_t w1 = __ballot(wc == 1), w2 = __ballot(wc == 2);
                     const uint32_t WcA = (uint32_t)__popc((uint32_t)w1) + 2u * (uint32_t)__popc((uint32_t)w2);
@@ -1328,7 +1470,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                     if (WcA + WcB > 0) {
                         const uint32_t pa = __builtin_amdgcn_mbcnt_lo((uint32_t)w1, 0u) + 2u * __builtin_amdgcn_mbcnt_lo((uint32_t)w2, 0u);
                         const uint32_t pb = __builtin_amdgcn_mbcnt_hi((uint32_t)(w1 >> 32), 0u) + 2u * __builtin_amdgcn_mbcnt_hi((uint32_t)(w2 >> 32), 0u);
-                        int32_t pos = (int32_t)(hi ? pb : pa);
+                        int32_t pos = (int32_t)(LEAN ? half(pa, pb) : (hi ? pb : pa));
                         const uint64_t nonstart = ~startmask & closedmask;  // never crosses lane 32 (forced start)
                         if (nonstart) {
                             const uint32_t packed = (it.ord << 2) | wc;
@@ -1344,9 +1486,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                                 run &= nonstart << d;
                             }
                         }
-                        uint32_t* rq = ring + (hi ? (size_t)cv.rc * 2 : 0);
-                        const uint32_t tl = hi ? tlB : tlA;
-                        const uint32_t mv0 = (se << 16) | sp;
+                        uint32_t* rq = ring + rq_off;
                         if (wc >= 1 && (uint32_t)pos < Kh) {
                             const uint32_t qi = (tl + (uint32_t)pos) & RCM;
                             rq[qi * 2] = mv0;
@@ -1361,13 +1501,19 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                     uint32_t emA = WcA < K0 ? WcA : K0, emB = WcB < K1 ? WcB : K1;
                     if (emA < K0 && moreA) {  // rare: leaf 0's source needs entries beyond its half
                         GC(3)
+                        ISA_MARK("pair_rest_begin");
+                        if constexpr (LEAN) ncA = 31u - (uint32_t)__clz(stA);  // (moreA)
                         const uint32_t jj = ncA + lane;
                         emA = gen_rest(0, seA, spA, lenA, kA, sxA, tlA, jj < dim ? (uint32_t)nb.keys[(size_t)sxA * dim + jj] : NBR_END, ncA, K0 - emA, emA);
+                        ISA_MARK("pair_rest_end");
                     }
                     if (emB < K1 && moreB) {
                         GC(4)
+                        ISA_MARK("pair_rest_begin");
+                        if constexpr (LEAN) ncB = 31u - (uint32_t)__clz(stB);  // (moreB)
                         const uint32_t jj = ncB + lane;
                         emB = gen_rest(1, seB, spB, lenB, kB, sxB, tlB, jj < dim ? (uint32_t)nb.keys[(size_t)sxB * dim + jj] : NBR_END, ncB, K1 - emB, emB);
+                        ISA_MARK("pair_rest_end");
                     }
                     C0.tail = tlA + emA;
                     C1.tail = tlB + emB;
@@ -1379,7 +1525,8 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                     LeafCursor c = l ? C1 : C0;
                     const uint32_t se = c.se, sp = c.sp, len = c.len, k = c.k, sx = c.sx;
                     // leaf 1 keeps its prefetched entries rotated by 32 lanes for the paired pass
-                    const uint32_t key = l ? __shfl(c.pk, (int)((lane + 32u) & 63u)) : c.pk;
+                    uint32_t key = row_key(l ? __shfl(c.pk, (int)((lane + 32u) & 63u)) : c.pk, lane);
+                    if constexpr (LEAN) asm volatile("" : "+v"(key)::"memory");  // taken before the next source's row load issues (as in the paired pass)
                     c.left -= 1;
                     c.o += 1;
                     if (c.left > 0) resolve(c, l);
@@ -1689,6 +1836,14 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                 p.trace_applied[4] = (int32_t)b;
                 p.trace_applied[5] = (int32_t)j;
                 p.trace_applied[6] = -1;
+            }
+            if constexpr (SAT) {
+                if (kind == 2 && a != b) {  // the one committed move that changes list lengths: a loses an element, b gains one
+                    const uint32_t la0 = uni(s_off[a + 1] - s_off[a]), lb0 = uni(s_off[b + 1] - s_off[b]);
+                    nsat += (lb0 == node_slot.pmax ? 1u : 0u);
+                    nsat -= (la0 == node_slot.pmax + 1u ? 1u : 0u);
+                }
+                nsat = uni(nsat);  // (the move's kind comes out of a shuffle: say that the count is wave-uniform, so the pass branches on a scalar)
             }
             apply_list_move_wave(m, s_visits, s_off, s_load, kind, a, i, b, j);
             {  // refresh node -> (route, position) for the two touched routes
