@@ -684,10 +684,29 @@ template <int L>
 struct LevelWords {
     uint32_t wc[L], wd[L];  // capacity / distance share of level k
     uint32_t has_cap;       // the capacity constraint exists (m.cap_level >= 0)
+    // The replay batch's other launch constants, one word each: taken from the argument struct where they are used, `capacity` and the two
+    // weights came back from spill lanes as the whole four-register groups their scalar loads had filled -- eight lane reads per batch for three
+    // words -- and the depot as a scalar load from the argument block, in every batch (RBATCH kernels).
+    int32_t cap, cw, dw;
+    uint32_t depot;
 };
-template <int L, bool USED>  // (USED = false: a kernel that never prices with eval_generated_small -- nothing is pinned)
+template <int L, bool USED, bool KW>  // (USED = false: a kernel that never prices with eval_generated_small -- nothing is pinned; KW: the constants as words too)
 __device__ __forceinline__ LevelWords<L> level_words(const ListModel& m) {
     LevelWords<L> w;
+    w.cap = w.cw = w.dw = 0;
+    w.depot = 0;
+    if constexpr (KW) {
+        // (through a vector register and back: pinned in place, a field stays a part of the register group its scalar load filled, and the group
+        // is what gets spilled and read back)
+        auto word = [](uint32_t v) -> uint32_t {
+            asm volatile("" : "+v"(v));
+            return uni(v);
+        };
+        w.cap = (int32_t)word((uint32_t)m.capacity);
+        w.cw = (int32_t)word((uint32_t)m.cap_weight);
+        w.dw = (int32_t)word((uint32_t)m.dist_weight);
+        w.depot = word((uint32_t)m.depot);
+    }
 #pragma unroll
     for (int k = 0; k < L; ++k) {
         w.wc[k] = uni(k == m.cap_level ? 0xFFFFFFFFu : 0u);
@@ -701,12 +720,12 @@ __device__ __forceinline__ LevelWords<L> level_words(const ListModel& m) {
     if constexpr (USED) asm volatile("" : "+s"(w.has_cap));
     return w;
 }
-template <int L, class LT, bool M16 = false, class OT = uint32_t>
+template <int L, class LT, bool M16 = false, class OT = uint32_t, bool KW = false>
 __device__ __forceinline__ void eval_generated_small(const ListModel& m, const LevelWords<L>& lw, const uint16_t* visits, const OT* off, const LT* load, uint32_t c,
                                                      uint32_t a, uint32_t i, uint32_t b, uint32_t j, int32_t (&dv)[L]) {
     const uint32_t oa = off[a], la = off[a + 1] - oa;
     const uint32_t ob = off[b], lb = off[b + 1] - ob;
-    const uint32_t depot = (uint32_t)m.depot;
+    const uint32_t depot = KW ? lw.depot : (uint32_t)m.depot;
     const uint32_t P = oa + i, Q = ob + j;
     // 1 when the neighbour exists (its position is then one step away; otherwise the read goes to the slot itself and the depot is selected)
     const uint32_t h_pa = min(i, 1u), h_na = min(la - 1u - i, 1u);      // i > 0 ; i + 1 < la   (i < la)
@@ -742,7 +761,7 @@ __device__ __forceinline__ void eval_generated_small(const ListModel& m, const L
         const int32_t dx = m.demand[x];
         const int32_t dyq = m.demand[vq];
         const int32_t dy = chg ? 0 : dyq;
-        const int32_t cap = (int32_t)m.capacity;
+        const int32_t cap = KW ? lw.cap : (int32_t)m.capacity;
         const int32_t la0 = (int32_t)load[a] - cap, lb0 = (int32_t)load[b] - cap;
         const int32_t sh = dx - dy;
         d_cap = max(la0 - sh, 0) + max(lb0 + sh, 0) - max(la0, 0) - max(lb0, 0);
@@ -753,7 +772,7 @@ __device__ __forceinline__ void eval_generated_small(const ListModel& m, const L
     const int32_t d_dist = (int32_t)(plus - minus);
     // penalties: score level -= weight * delta(penalty sum); a level's share is picked with a 32-bit all-ones / zero word per (level, constraint) --
     // two wave-uniform words (LevelWords) instead of a lane mask in a scalar register pair and a select each
-    const int32_t tc = -((int32_t)m.cap_weight * d_cap), td = -((int32_t)m.dist_weight * d_dist);
+    const int32_t tc = -((KW ? lw.cw : (int32_t)m.cap_weight) * d_cap), td = -((KW ? lw.dw : (int32_t)m.dist_weight) * d_dist);
 #pragma unroll
     for (int k = 0; k < L; ++k) dv[k] = (int32_t)(((uint32_t)tc & lw.wc[k]) + ((uint32_t)td & lw.wd[k]));
 }
@@ -822,6 +841,10 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
     // compile the pass they had.  (How each of the five was built and measured on its own: profiles/wave_pair_levers.txt.)
     constexpr bool LEAN = FAST && SMALL;
     constexpr bool SAT = LEAN && COMPACT, RANKTAB = LEAN && COMPACT && !NODEG;
+    // RBATCH: the lean replay batch of DESIGN 18 (the AcceptedCount cut and the quit test behind one compare on the batch's accepted count,
+    // candidates_scored once per step, the batch's launch constants as pinned words) -- the LEAN kernels that keep the node table in LDS.  The NODEG
+    // kernel (launch mode 6) compiles the batch it had: with the same source form its CVRP-5000 leg measured 2.0 % SLOWER than its parent.
+    constexpr bool RBATCH = LEAN && !NODEG;
 // A cold field of `p` / `m`: the FAST + SMALL kernels -- the ones whose bound is the scalar unit -- read it from the argument block where it
 // is used, the others from the by-value structs.  (Local to this kernel: the macros name its `SMALL`, `p` and `m`, and end with it.)
 #define SF_COLD_P(f) (SMALL ? cold_args()->p.f : p.f)
@@ -969,7 +992,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
     auto half = [&](uint32_t lo, uint32_t up) -> uint32_t { return (lo & ~hm) | (up & hm); };
     PH_DECL
 
-    const LevelWords<L> lvl = level_words<L, SMALL>(m);
+    const LevelWords<L> lvl = level_words<L, SMALL, RBATCH>(m);
     bool best_pending = false;  // working == best, snapshot not yet written (see sf_scalar_kernels.hip: deferred clone)
     const FastMod fm_V = make_fastmod(V > 0 ? (uint32_t)V : 1u);
     const FastMod fm_V1 = make_fastmod(V > 1 ? (uint32_t)V - 1u : 1u);
@@ -1595,7 +1618,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                         m0 = rq[0];
                         m1 = rq[1];
                         const uint32_t a = m0 >> 16, i = m0 & 0xFFFFu, b = m1 >> 16, j = m1 & 0xFFFFu;
-                        eval_generated_small<L, LT, COMPACT, OT>(m, lvl, s_visits, s_off, s_load, 1u - lfq, a, i, b, j, dv);  // FAST: leaf 0 = change, leaf 1 = swap; COMPACT reads the u16 matrix
+                        eval_generated_small<L, LT, COMPACT, OT, RBATCH>(m, lvl, s_visits, s_off, s_load, 1u - lfq, a, i, b, j, dv);  // FAST: leaf 0 = change, leaf 1 = swap; COMPACT reads the u16 matrix
                     }
                     doable = valid;
                     // LateAcceptance: score >= last step score || score >= late score (late_acceptance.rs:89-125).  Two levels: the pair of int32 deltas
@@ -1609,15 +1632,29 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                         acc = valid && (small_ge0<L>(dv) || small_ge<L>(dv, late_d));
                     }
                     accmask = __ballot(acc);
-                    {  // AcceptedCount quota (forager.rs:232-239)
+                    // AcceptedCount quota (forager.rs:232-239): the step ends at the lane whose accepted candidate is the limit-th.  That lane exists
+                    // only in a batch with at least `remaining` accepted lanes -- the step's last one, one batch in ten at the default limit -- so one
+                    // wave-uniform compare on the batch's count (formed for `accepted` anyway) stands in front of the prefix count, the second
+                    // ballot and the re-masking; every other batch consumes its nvalid lanes, and `acc` (valid lanes only) is final as it stands.
+                    // `>=`: 64 accepted lanes with exactly 64 remaining do cut, at lane 63.  The same compare IS the forager's quit test.  Precondition:
+                    // FAST implies forager == FORAGER_ACCEPTED_COUNT (host-checked), whose forager_quits is `accepted >= limit`, and the host keeps
+                    // p.limit >= 1 for it; `accepted` never passes the limit.  A batch with at least `remaining` accepted lanes always holds the
+                    // limit-th accepted lane, so the cut fires in it, `accepted` becomes `limit` and the step ends; a batch with fewer leaves
+                    // `accepted` below the limit.  Cut and quit coincide: the step's end is decided here, not a second time at the batch's end.
+                    consumed = valid;
+                    if (!RBATCH || (uint32_t)__popcll(accmask) >= (uint32_t)p.limit - accepted) {
                         const uint32_t remaining = (uint32_t)p.limit - accepted;
                         const uint32_t pre = mbcnt64(accmask) + (acc ? 1u : 0u);
                         const uint64_t cutmask = __ballot(acc && pre == remaining);
                         nconsumed = cutmask ? (uint32_t)__ffsll((unsigned long long)cutmask) : nvalid;
+                        consumed = lane < nconsumed;
+                        acc = acc && consumed;
+                        accmask = __ballot(acc);
+                        if constexpr (RBATCH) {
+                            st_scored += nvalid - nconsumed;  // scored but not consumed (candidates_scored is added once per step, from `pulls`)
+                            done = 1;
+                        }
                     }
-                    consumed = lane < nconsumed;
-                    acc = acc && consumed;
-                    accmask = __ballot(acc);
                     bool challenger;
                     if constexpr (L == 2)
                         challenger = acc && key >= best_key;
@@ -1758,7 +1795,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                 }
                 const uint32_t nacc = (uint32_t)__popcll(accmask);
                 accepted += nacc;
-                st_scored += nvalid;
+                if constexpr (!RBATCH) st_scored += nvalid;  // (RBATCH: a batch scores what it consumes except where the quota cuts it -- added once per step from `pulls`, the cut's remainder at the cut)
                 if constexpr (!SMALL) {  // (SMALL: moves_generated / accepted are added once per step from `pulls` / `accepted`; every candidate is doable)
                     st_gen += nconsumed;
                     st_acc += nacc;
@@ -1790,7 +1827,8 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                 C1.head += c1;
                 C0.head += nconsumed - c1;
                 pulls += nconsumed;
-                if (forager_quits(forager, (uint32_t)p.limit, accepted, has_best, improving_pick)) done = 1;
+                if constexpr (!RBATCH)  // (RBATCH: decided at the cut)
+                    if (forager_quits(forager, (uint32_t)p.limit, accepted, has_best, improving_pick)) done = 1;
             }
             ISA_MARK("replay_end");
             PH(3)
@@ -1907,6 +1945,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                 st_gen += pulls;
                 st_calc += pulls;
                 st_acc += accepted;
+                if constexpr (RBATCH) st_scored += pulls;
             }
             la_cursor = la_cursor + 1 >= la_size ? 0 : la_cursor + 1;
             const int64_t move_budget = SF_COLD_P(move_budget);
