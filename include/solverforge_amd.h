@@ -672,6 +672,51 @@ int32_t sf_construct_list_round_robin(sf_ctx* ctx, int32_t descriptor_index, con
 int32_t sf_construct_list_clarke_wright(sf_ctx* ctx, int32_t descriptor_index, const uint32_t* elements, int32_t n, int32_t feasible_mode,
                                         int64_t* out_scores, int32_t* out_committed);
 
+/* solverforge_config::ConstructionHeuristicType, the nine scalar heuristics in declaration order (crates/solverforge-config/src/phase.rs:92-123) */
+typedef enum sf_construction_heuristic {
+    SF_CH_FIRST_FIT = 0,
+    SF_CH_FIRST_FIT_DECREASING = 1,      /* needs entity_order_keys */
+    SF_CH_WEAKEST_FIT = 2,               /* needs value_order_keys */
+    SF_CH_WEAKEST_FIT_DECREASING = 3,    /* needs both */
+    SF_CH_STRONGEST_FIT = 4,             /* needs value_order_keys */
+    SF_CH_STRONGEST_FIT_DECREASING = 5,  /* needs both */
+    SF_CH_CHEAPEST_INSERTION = 6,
+    SF_CH_ALLOCATE_ENTITY_FROM_QUEUE = 7, /* needs entity_order_keys */
+    SF_CH_ALLOCATE_TO_VALUE_FROM_QUEUE = 8 /* needs value_order_keys */
+} sf_construction_heuristic;
+/* solverforge_config::ConstructionObligation (phase.rs:82-90) */
+typedef enum sf_construction_obligation { SF_CO_PRESERVE_UNASSIGNED = 0, SF_CO_ASSIGN_WHEN_CANDIDATE_EXISTS = 1 } sf_construction_obligation;
+typedef struct sf_scalar_construction_config {
+    int32_t heuristic;             /* sf_construction_heuristic */
+    int32_t obligation;            /* sf_construction_obligation */
+    int32_t value_candidate_limit; /* the canonical value list of an entity is cut to its first `limit` values; 0 = none */
+    int32_t reserved;              /* 0.  Bit 0 = value_order_keys depend on the entity ([n_rows * n_values]): not built, SF_ERR_UNSUPPORTED */
+} sf_scalar_construction_config;
+
+/* ≙ ConstructionHeuristicPhase over one scalar variable (crates/solverforge-solver/src/phase/construction/: the heuristic's entity
+ * order, value order, forager and live refresh runtime_slots/placement.rs:73-147, the placement cursor placement.rs:307-368 and
+ * placer/queued.rs:242-295, the foragers forager_step.rs:149-332,463-625 with decision.rs:50-154, the commit phase/selection.rs:14-86)
+ * on EVERY replica's current values, one wavefront per replica.  The entities are taken in the heuristic's order -- canonical, or a
+ * stable sort by entity_order_keys[n_rows] (descending for the *_DECREASING heuristics, ascending for ALLOCATE_ENTITY_FROM_QUEUE, ties
+ * by index); an entity that holds a value or whose value list is empty is skipped.  Its candidates are the change moves to its
+ * canonical values (sf_schema_set_value_lists, else 0..n_values) cut to value_candidate_limit, for ALLOCATE_TO_VALUE_FROM_QUEUE then
+ * stably sorted by value_order_keys[n_values].  Keep-current is a choice only when the variable allows unassigned AND the obligation is
+ * PRESERVE_UNASSIGNED; then the committed score is the baseline.  First fit takes the first doable candidate whose trial score is
+ * strictly above the baseline (without one: the first doable candidate, unscored); CHEAPEST_INSERTION the strictly best trial score,
+ * the first of equals, and keeps current only when the baseline is strictly greater; weakest / strongest fit the doable candidate of
+ * least / greatest value_order_keys[value], first of equals, scored once and taken only if strictly above the baseline when there is
+ * one.  FIRST_FIT and CHEAPEST_INSERTION make one pass; the other seven reopen the cursor at the head of the order after every step
+ * (live refresh), where an entity that kept current counts as completed only at the solution revision it kept at (frontier.rs:32-50):
+ * every assignment makes the entities that kept current before it candidates again, in order.  Counters: one generated + evaluated
+ * candidate per pulled candidate (not-doable ones included), one score_calculation per trial, one accepted + applied move per
+ * assignment, one step per placement whether it assigned or kept (phase/phase_type.rs:108-148).  A key array the heuristic needs and
+ * does not get, a bad enum value or a variable that is not the class's scalar variable is SF_ERR_INVALID; a context that declares
+ * SF_C_CROSS_OWNER_MATCH and entity-dependent value keys are SF_ERR_UNSUPPORTED; the grouped-scalar assignment construction
+ * (phase/construction/grouped_scalar/) is not part of this call.  The scalar class of a mixed model without that join is served.
+ * Commits the score of the constructed values; out_scores[n_replicas * score_levels] may be NULL. */
+int32_t sf_construct_scalar(sf_ctx* ctx, int32_t descriptor_index, int32_t variable_index, const sf_scalar_construction_config* cfg,
+                            const int64_t* entity_order_keys, const int64_t* value_order_keys, int64_t* out_scores);
+
 /* ---- MoveSelector / cursor surface ------------------------------------------------------- */
 /* Opens the configured union cursor for MoveStreamContext(step_index, step_seed) with the given
  * selection order on replica `replica`, drains it, and returns every candidate in cursor order

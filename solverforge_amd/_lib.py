@@ -53,6 +53,10 @@ class StatsStruct(C.Structure):
         "score_calculations", "moves_not_doable", "candidates_scored", "sources_scanned", "reserved")]
 
 
+class ScalarConstructionConfigStruct(C.Structure):
+    _fields_ = [("heuristic", C.c_int32), ("obligation", C.c_int32), ("value_candidate_limit", C.c_int32), ("reserved", C.c_int32)]
+
+
 class TraceDigestStruct(C.Structure):
     _fields_ = [("first", C.c_uint64), ("second", C.c_uint64)]
 
@@ -71,7 +75,7 @@ SYMBOLS = [
     "sf_ctx_create", "sf_ctx_destroy", "sf_last_error", "sf_device_count", "sf_sync",
     "sf_schema_add_entity_class", "sf_schema_add_scalar_variable", "sf_schema_add_list_variable",
     "sf_fact_matrix_i64", "sf_fact_column_i32", "sf_fact_column_u32", "sf_fact_csr_u32",
-    "sf_constraint_add", "sf_constraint_add_list_precedence", "sf_selector_add", "sf_selector_add_sublist", "sf_selector_add_kopt", "sf_selector_add_permute", "sf_selector_add_precedence", "sf_list_set_precedence_policy", "sf_selector_add_ruin", "sf_selector_add_nearby_scalar", "sf_step_evaluate_compound", "sf_step_decide", "sf_step_decide_gated", "sf_step_decide_cursor", "sf_apply_compound", "sf_construct_list_cheapest", "sf_construct_list_regret", "sf_construct_list_clarke_wright", "sf_construct_list_round_robin", "sf_construct_list_k_opt", "sf_list_set_time_windows", "sf_list_routes_feasible", "sf_list_time_window_path", "sf_list_force_time_window_walk", "sf_union_configure", "sf_schema_set_value_lists", "sf_initialize", "sf_evaluate_all", "sf_evaluate_each", "sf_get_scores",
+    "sf_constraint_add", "sf_constraint_add_list_precedence", "sf_selector_add", "sf_selector_add_sublist", "sf_selector_add_kopt", "sf_selector_add_permute", "sf_selector_add_precedence", "sf_list_set_precedence_policy", "sf_selector_add_ruin", "sf_selector_add_nearby_scalar", "sf_step_evaluate_compound", "sf_step_decide", "sf_step_decide_gated", "sf_step_decide_cursor", "sf_apply_compound", "sf_construct_list_cheapest", "sf_construct_list_regret", "sf_construct_list_clarke_wright", "sf_construct_list_round_robin", "sf_construct_list_k_opt", "sf_construct_scalar", "sf_list_set_time_windows", "sf_list_routes_feasible", "sf_list_time_window_path", "sf_list_force_time_window_walk", "sf_union_configure", "sf_schema_set_value_lists", "sf_initialize", "sf_evaluate_all", "sf_evaluate_each", "sf_get_scores",
     "sf_step_evaluate", "sf_apply", "sf_step_generate", "sf_solver_configure", "sf_default_local_search_components", "sf_solver_configure_default", "sf_solver_configure_annealing", "sf_solver_configure_diversified",
     "sf_get_annealing_state", "sf_solver_set_step_seeds",
     "sf_solver_set_engine", "sf_solver_get_engine", "sf_list_wave_layout", "sf_list_arith_flags", "sf_constraint_add_pair_join", "sf_constraint_add_uni_program", "sf_provider_declare", "sf_phase_start", "sf_solve_steps", "sf_solve_moves", "sf_solve_step_traced", "sf_get_stats", "sf_get_stats_sum", "sf_get_best_scores",
@@ -136,6 +140,7 @@ def load():
     L.sf_construct_list_clarke_wright.argtypes = [vp, i32, vp, i32, i32, vp, vp]
     L.sf_construct_list_round_robin.argtypes = [vp, i32, vp, i32, vp, vp, vp]
     L.sf_construct_list_k_opt.argtypes = [vp, i32, i32, i32, i32, vp]
+    L.sf_construct_scalar.argtypes = [vp, i32, i32, C.POINTER(ScalarConstructionConfigStruct), vp, vp, vp]
     L.sf_list_set_time_windows.argtypes = [vp, i32, i32, vp, vp, vp, vp, i64]
     L.sf_list_routes_feasible.argtypes = [vp, i32, i32, vp]
     L.sf_list_time_window_path.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]

@@ -21,6 +21,7 @@
 #include "sf_clarke_wright.hip"
 #include "sf_kopt_tw.hip"
 #include "sf_precedence.hip"
+#include "sf_scalar_construct.h"
 
 using namespace sf;
 
@@ -2305,5 +2306,6 @@ extern "C" int32_t sf_debug_phases(uint64_t* out8) {  // diagnostic builds only 
 #include "sf_api_scalar.inc"
 #include "sf_api_moves.inc"
 #include "sf_api_construct.inc"
+#include "sf_api_scalar_construct.inc"
 #include "sf_portfolio.inc"
 #include "sf_candidate_trace.inc"

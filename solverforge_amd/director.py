@@ -12,7 +12,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import MOVE_DTYPE, AnnealingConfigStruct, SolverConfigStruct, SolverForgeError, StatsStruct, check, ptr
+from ._lib import (MOVE_DTYPE, AnnealingConfigStruct, ScalarConstructionConfigStruct, SolverConfigStruct, SolverForgeError, StatsStruct,
+                   check, ptr)
 
 
 class MoveKind:
@@ -49,6 +50,15 @@ class Forager:
     ACCEPTED_COUNT, FIRST_ACCEPTED, BEST_SCORE = 0, 1, 2
     # forager/improving.rs: quit at the first accepted candidate better than the best-ever / last-step score
     FIRST_BEST_SCORE_IMPROVING, FIRST_LAST_STEP_SCORE_IMPROVING = 3, 4
+
+
+class ConstructionHeuristic:  # sf_construction_heuristic: solverforge_config::ConstructionHeuristicType, the scalar ones in declaration order
+    FIRST_FIT, FIRST_FIT_DECREASING, WEAKEST_FIT, WEAKEST_FIT_DECREASING, STRONGEST_FIT, STRONGEST_FIT_DECREASING = 0, 1, 2, 3, 4, 5
+    CHEAPEST_INSERTION, ALLOCATE_ENTITY_FROM_QUEUE, ALLOCATE_TO_VALUE_FROM_QUEUE = 6, 7, 8
+
+
+class ConstructionObligation:  # sf_construction_obligation
+    PRESERVE_UNASSIGNED, ASSIGN_WHEN_CANDIDATE_EXISTS = 0, 1
 
 
 class Engine:  # sf_engine_kind
@@ -131,6 +141,7 @@ class GpuScoreDirector:
         self.n_replicas = n_replicas
         self._entity_counts = {}
         self._list_capacity = {}
+        self._value_counts = {}
         self._keep = []
 
     def close(self):
@@ -157,6 +168,7 @@ class GpuScoreDirector:
                                    f"({n_rows}), got shape {initial.shape}")
         check(self._L.sf_schema_add_scalar_variable(self._h, descriptor_index, variable_index, n_values,
                                                     int(allows_unassigned), ptr(initial)), self._h)
+        self._value_counts[(descriptor_index, variable_index)] = n_values
 
     def set_value_lists(self, descriptor_index, variable_index, lists):
         """ValueSource::EntitySlice: `lists[e]` = the canonical value list of entity e (values in 0..n_values)."""
@@ -492,6 +504,29 @@ class GpuScoreDirector:
         flags = np.zeros(self.n_replicas, dtype=np.int32)
         check(self._L.sf_construct_list_clarke_wright(self._h, descriptor_index, ptr(el), len(el), int(feasible_mode), ptr(out), ptr(flags)), self._h)
         return out, flags
+
+    def construct_scalar(self, descriptor_index=0, variable_index=0, heuristic=ConstructionHeuristic.FIRST_FIT,
+                         obligation=ConstructionObligation.PRESERVE_UNASSIGNED, value_candidate_limit=0, entity_order_keys=None,
+                         value_order_keys=None):
+        """≙ ConstructionHeuristicPhase over the scalar variable on every replica's current values (sf_construct_scalar): the unassigned
+        entities in the heuristic's order (entity_order_keys[n_rows] for the *_DECREASING heuristics and ALLOCATE_ENTITY_FROM_QUEUE)
+        each take the value its forager picks among the entity's canonical values cut to value_candidate_limit (0 = none);
+        value_order_keys[n_values] = the strength of a value (weakest / strongest fit) or the value order of
+        ALLOCATE_TO_VALUE_FROM_QUEUE.  A nullable variable keeps current unless a candidate beats the committed score, except under
+        ASSIGN_WHEN_CANDIDATE_EXISTS.  Returns the committed scores [n_replicas, levels]."""
+        n_rows = self._entity_counts.get(descriptor_index)
+        ek = None if entity_order_keys is None else np.ascontiguousarray(entity_order_keys, dtype=np.int64)
+        vk = None if value_order_keys is None else np.ascontiguousarray(value_order_keys, dtype=np.int64)
+        if ek is not None and ek.shape != (n_rows,):  # the C side reads n_rows keys
+            raise SolverForgeError(f"SF_ERR_INVALID: entity_order_keys must hold one key per row of class {descriptor_index} ({n_rows})")
+        n_values = self._value_counts.get((descriptor_index, variable_index))
+        if vk is not None and vk.shape != (n_values,):  # ... and n_values keys
+            raise SolverForgeError(f"SF_ERR_INVALID: value_order_keys must hold one key per value of the variable ({n_values})")
+        cfg = ScalarConstructionConfigStruct(int(heuristic), int(obligation), int(value_candidate_limit), 0)
+        out = np.zeros((self.n_replicas, self.levels), dtype=np.int64)
+        check(self._L.sf_construct_scalar(self._h, descriptor_index, variable_index, C.byref(cfg), None if ek is None else ptr(ek),
+                                          None if vk is None else ptr(vk), ptr(out)), self._h)
+        return out
 
     # ---- MoveSelector / cursor surface ---------------------------------------------------
     def open_cursor(self, step_index, step_seed, selection_order=SelectionOrder.RANDOM, replica=0, cap=1 << 16):
