@@ -1340,8 +1340,8 @@ static int run_evaluate_all(sf_ctx* ctx, int64_t* out, int commit, int64_t* d_pa
                            ctx->d_scores_out, commit, d_parts);
     }
     if (ctx->has_scalar_model)  // mixed model: the scalar class adds its constraints to the list class's scores
-        hipLaunchKernelGGL(k_scalar_evaluate_all, dim3(ctx->R), dim3(256), scalar_table_bytes(ctx), ctx->stream, ctx->sm,
-                           ctx->d_scores_out, commit, ctx->has_list_model ? 1 : 0, d_parts);
+        HIPCHK(ctx, launch_with_lds(k_scalar_evaluate_all, dim3(ctx->R), dim3(256), scalar_table_bytes(ctx), ctx->stream, ctx->sm, ctx->d_scores_out, commit,
+                                    ctx->has_list_model ? 1 : 0, d_parts));
     if (ctx->xown_level >= 0)  // the join of the two planning classes adds its level
         hipLaunchKernelGGL(k_cross_owner_evaluate_all, dim3(ctx->R), dim3(256), 0, ctx->stream, ctx->lm, ctx->sm.vals, ctx->sm.n, ctx->xown_level, ctx->xown_weight,
                            ctx->d_scores_out, commit, d_parts);

@@ -67,7 +67,7 @@ int32_t sf_step_evaluate(sf_ctx* ctx, int32_t replica, const sf_move_t* moves, i
     if (ctx->has_list_model)
         hipLaunchKernelGGL(k_list_evaluate_moves, dim3(grid), dim3(256), 0, ctx->stream, ctx->lm, replica, d_moves, n, d_sc.p, d_do.p, mixed);
     if (ctx->has_scalar_model)
-        hipLaunchKernelGGL(k_scalar_evaluate_moves, dim3(grid), dim3(256), scalar_table_bytes(ctx), ctx->stream, ctx->sm, replica, d_moves, n, d_sc.p, d_do.p, mixed);
+        HIPCHK(ctx, launch_with_lds(k_scalar_evaluate_moves, dim3(grid), dim3(256), scalar_table_bytes(ctx), ctx->stream, ctx->sm, replica, d_moves, n, d_sc.p, d_do.p, mixed));
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && ctx->has_list_model) {  // list ruin moves: scored by their own kernel, one wavefront per move
         std::vector<int32_t> which;
@@ -136,8 +136,8 @@ int32_t sf_step_evaluate_compound(sf_ctx* ctx, int32_t replica, const sf_move_t*
         (rc = d_do.alloc(ctx, (size_t)n)))
         return rc;
     const int32_t* d_edits = (const int32_t*)d_rec.p;
-    hipLaunchKernelGGL(k_scalar_evaluate_compound, dim3((int)((n + 255) / 256)), dim3(256), scalar_table_bytes(ctx), ctx->stream, ctx->sm, replica,
-                       d_edits, d_off.p, n, d_sc.p, d_do.p);
+    HIPCHK(ctx, launch_with_lds(k_scalar_evaluate_compound, dim3((int)((n + 255) / 256)), dim3(256), scalar_table_bytes(ctx), ctx->stream, ctx->sm, replica, d_edits,
+                                d_off.p, n, d_sc.p, d_do.p));
     if (ctx->xown_level >= 0) {  // the join of the two planning classes: a scalar edit changes the A side's key
         hipLaunchKernelGGL(k_cross_owner_holders, dim3(1), dim3(256), 0, ctx->stream, ctx->lm, replica, ctx->sm.n, ctx->d_xown_tab);
         hipLaunchKernelGGL(k_cross_owner_evaluate_compound, dim3((int)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->sm.vals, ctx->sm.n, ctx->d_xown_tab, replica, d_edits,
@@ -193,8 +193,8 @@ int32_t sf_apply_compound(sf_ctx* ctx, int32_t replica, const sf_move_t* edits, 
     if ((rc = d_edits.upload(ctx, edits, (size_t)n_edits))) return rc;
     const int64_t one_candidate[2] = {0, n_edits};
     if ((rc = xown_price(ctx, replica, edits, n_edits, one_candidate))) return rc;
-    hipLaunchKernelGGL(k_scalar_apply_compound, dim3(1), dim3(64), scalar_table_bytes(ctx), ctx->stream, ctx->sm, replica, (const int32_t*)d_edits.p, (int)n_edits,
-                       ctx->d_ok);
+    HIPCHK(ctx, launch_with_lds(k_scalar_apply_compound, dim3(1), dim3(64), scalar_table_bytes(ctx), ctx->stream, ctx->sm, replica, (const int32_t*)d_edits.p,
+                                (int)n_edits, ctx->d_ok));
     xown_commit(ctx, replica);
     int32_t ok = 0;
     hipError_t e = hipGetLastError();
@@ -312,10 +312,10 @@ static int32_t step_decide_impl(sf_ctx* ctx, int32_t replica, const sf_move_t* e
     if (!kgates.empty() && (rc = d_gates.upload(ctx, kgates.data(), kgates.size()))) return rc;
     const int32_t* d_edits = (const int32_t*)d_rec.p;
     if (nk > 0)
-        hipLaunchKernelGGL(k_scalar_evaluate_compound, dim3((int)((nk + 255) / 256)), dim3(256), scalar_table_bytes(ctx), ctx->stream, ctx->sm, replica, d_edits,
-                           d_off.p, nk, d_sc.p, d_do.p);
-    hipLaunchKernelGGL(k_scalar_step_decide, dim3(1), dim3(64), scalar_table_bytes(ctx), ctx->stream, ctx->sm, p, replica, d_edits, d_off.p, nk, d_sc.p, d_do.p, d_fl.p,
-                       d_res.p, (const int32_t*)d_gates.p, ctx->hard_levels);
+        HIPCHK(ctx, launch_with_lds(k_scalar_evaluate_compound, dim3((int)((nk + 255) / 256)), dim3(256), scalar_table_bytes(ctx), ctx->stream, ctx->sm, replica, d_edits,
+                                    d_off.p, nk, d_sc.p, d_do.p));
+    HIPCHK(ctx, launch_with_lds(k_scalar_step_decide, dim3(1), dim3(64), scalar_table_bytes(ctx), ctx->stream, ctx->sm, p, replica, d_edits, d_off.p, nk, d_sc.p, d_do.p,
+                                d_fl.p, d_res.p, (const int32_t*)d_gates.p, ctx->hard_levels));
     hipError_t e = hipGetLastError();
     int64_t res[2] = {0, -1};
     if (e == hipSuccess) e = hipMemcpyAsync(res, d_res.p, 16, hipMemcpyDeviceToHost, ctx->stream);
@@ -427,8 +427,8 @@ int32_t sf_apply(sf_ctx* ctx, int32_t replica, const sf_move_t* mv) {
             hipLaunchKernelGGL(k_prec_after_apply, dim3(1), dim3(64), 0, ctx->stream, ctx->lm, ctx->pm, replica);
     } else {
         if ((rc = xown_price(ctx, replica, mv, 1, nullptr))) return rc;
-        hipLaunchKernelGGL(k_scalar_apply, dim3(1), dim3(64), scalar_table_bytes(ctx), ctx->stream, ctx->sm, replica, mv->kind, mv->a,
-                           mv->b, mv->value, ctx->d_ok);
+        HIPCHK(ctx, launch_with_lds(k_scalar_apply, dim3(1), dim3(64), scalar_table_bytes(ctx), ctx->stream, ctx->sm, replica, mv->kind, mv->a, mv->b, mv->value,
+                                    ctx->d_ok));
     }
     xown_commit(ctx, replica);
     HIPCHK(ctx, hipGetLastError());

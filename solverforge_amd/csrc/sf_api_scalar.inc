@@ -439,6 +439,11 @@ static int build_scalar_model(sf_ctx* ctx, int d) {
         m.n_xj = (int32_t)joins.size();
     }
     if ((rc = compile_uni_programs(ctx, d, m))) return rc;
+    // The host-driven kernels of the class (evaluate_all, step evaluate / apply / decide, the construction) keep the per-value tables in
+    // the dynamic LDS of one launch, next to at most 1 KiB of static LDS: a class they cannot be launched with is refused here, before
+    // any of them runs (DESIGN §14).
+    if (scalar_table_bytes(ctx) > SF_LDS_BUDGET)
+        return fail(ctx, SF_ERR_UNSUPPORTED, "the per-value tables of the scalar class (12 bytes per value, plus the runs table) do not fit the LDS of one launch");
     if (!c.value_off.empty()) {
         uint32_t* d_off = nullptr;
         int32_t* d_vl = nullptr;

@@ -305,3 +305,253 @@ def keys(n, mod, seed):
     from solverforge_amd import datasets
 
     return (datasets.stream(seed, n) % np.uint64(mod)).astype(np.int64)
+
+
+# ---- placements wider than one 64-lane chunk ----------------------------------------------------------------------------------------------
+WIDE = 130                                   # two full chunks and a tail of two
+BEST_FIT_ORDINALS = [0, 63, 64, 65, 127, 128, 129]
+BEST_FIT_VALUES = BEST_FIT_ORDINALS + [10, 70, 0]  # what CheapestInsertion gives entities 0..9 of best_fit_assignment(ex_level=-1)
+
+
+def best_fit_assignment(ex_level=-1, n=24):
+    """A cost matrix whose best entry sits at a chosen ordinal of a 130-value placement: every cost is in 5..8 (seeded, so the other entities
+    tie inside and across chunks), entity e < 7 has its only cost 1 at BEST_FIT_ORDINALS[e], entity 7 has cost 1 at ordinals 10 AND 70 (the
+    first wins), entity 8 has cost 2 at 10 and cost 1 at 70 (the later, better one wins), entity 9 has all costs equal (ordinal 0 wins).
+    ex_level=-1: no exists node (no per-value tables); ex_level=0: opening a row costs one hard, as in retry_assignment -- every cost is
+    positive, so under PreserveUnassigned the baseline beats every one of the 130 trials."""
+    import solverforge_amd as sfa
+    from solverforge_amd import datasets
+
+    cost = (datasets.stream(41, n * WIDE) % np.uint64(4)).astype(np.int64).reshape(n, WIDE) + 5
+    for e, k in enumerate(BEST_FIT_ORDINALS):
+        cost[e, k] = 1
+    cost[7, 10] = cost[7, 70] = 1
+    cost[8, 10], cost[8, 70] = 2, 1
+    cost[9, :] = 6
+    row_w = np.ones(WIDE, dtype=np.int64)
+
+    def gpu(start, R, nullable):
+        assert nullable
+        return sfa.build_assignment(start, cost, WIDE, n_replicas=R, row_w=row_w, ex_level=ex_level)
+
+    return Case(f"bestfit{ex_level}", n, WIDE, lambda sfo, start: sfo.Model.assignment(start, cost, WIDE, row_w=row_w, ex_level=ex_level), gpu)
+
+
+INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
+
+
+def strength_keys(weakest):
+    """name -> (value keys of a 130-value range, value_candidate_limit, the ordinal every placement must take) for the weakest-fit
+    (weakest=True: the extreme is the least key) or the strongest-fit heuristics.  The sentinel rows make every key equal to what the
+    kernel puts on the invalid lanes of a ragged last chunk."""
+    ext, sentinel = (-7, INT64_MAX) if weakest else (7, INT64_MIN)
+    base = (np.arange(WIDE, dtype=np.int64) * 5) % 3  # 0..2, with ties everywhere
+
+    def at(*ordinals):
+        k = base.copy()
+        k[list(ordinals)] = ext
+        return k
+
+    return {
+        "at64": (at(64), 0, 64), "at127": (at(127), 0, 127), "at129": (at(129), 0, 129),
+        "twice_in_two_chunks": (at(70, 128), 0, 70), "twice_from_lane63": (at(63, 64), 0, 63),
+        "all_equal": (np.full(WIDE, 4, dtype=np.int64), 0, 0),
+        "sentinel65": (np.full(WIDE, sentinel, dtype=np.int64), 65, 0), "sentinel130": (np.full(WIDE, sentinel, dtype=np.int64), 0, 0),
+    }
+
+
+WIDE_STRONGEST, WIDE_WEAKEST = 77, 33   # the values that carry the only greatest / the only least key of wide_list_keys()
+WIDE_LENGTHS = [1, 63, 64, 65, 128, 129, 130]
+# entity -> (list length, ordinal of WIDE_STRONGEST, ordinal of WIDE_WEAKEST): lane 0 and lane 63 of the later chunks, and the last ordinals
+WIDE_PLACED = {0: (130, 64, 127), 1: (130, 127, 64), 2: (129, 128, 0), 3: (128, 5, 127), 4: (65, 64, 3), 5: (64, 63, 0), 6: (63, 62, 1),
+               7: (130, 129, 128), 8: (130, 0, 129)}
+
+
+def wide_list_keys():
+    """Value keys with ties and one greatest (WIDE_STRONGEST) and one least (WIDE_WEAKEST) value."""
+    from solverforge_amd import datasets
+
+    k = (datasets.stream(43, WIDE) % np.uint64(9)).astype(np.int64)
+    k[WIDE_STRONGEST], k[WIDE_WEAKEST] = 100, -100
+    return k
+
+
+def wide_lists(n, seed=47):
+    """Per-entity value lists of the lengths 1, 63, 64, 65, 128, 129 and 130 in a seeded order, each a seeded arrangement of distinct values of
+    the 130-value range; the entities of WIDE_PLACED carry the two extreme values of wide_list_keys() at the ordinals named there."""
+    from solverforge_amd import datasets
+
+    r = datasets.stream(seed, n * WIDE).reshape(n, WIDE)
+    pick = datasets.stream(seed + 1, n)
+    lists = []
+    for e in range(n):
+        full = np.argsort(r[e], kind="stable").tolist()
+        if e in WIDE_PLACED:
+            length, at_strong, at_weak = WIDE_PLACED[e]
+            rest = [v for v in full if v not in (WIDE_STRONGEST, WIDE_WEAKEST)][:length - 2]
+            lst = [None] * length
+            lst[at_strong], lst[at_weak] = WIDE_STRONGEST, WIDE_WEAKEST
+            it = iter(rest)
+            lst = [next(it) if v is None else v for v in lst]
+        else:
+            lst = full[:WIDE_LENGTHS[int(pick[e] % np.uint64(len(WIDE_LENGTHS)))]]
+        lists.append([int(v) for v in lst])
+    return lists
+
+
+def wide_assignment(n=24, value_lists=None):
+    """assignment() at 130 rows: the cost join and the exists node (the per-value tables hold 130 values)."""
+    return assignment(n=n, n_values=WIDE, seed=53, value_lists=value_lists)
+
+
+def wide_clique(n, value_lists=None):
+    """A clique with 130 colours: the first-fit forager of entity i has to pass the i colours that are taken."""
+    off, adj = _clique(n)
+    return _graph_case(f"clique{n}x{WIDE}", {"n": n, "n_colors": WIDE, "adj_off": off, "adj": adj}, value_lists)
+
+
+# entity -> the ordinal at which its first strictly-improving candidate must fall
+ROTATED_HITS_70 = {63: 63, 66: 64, 69: 63, 68: 64}
+ROTATED_HITS_130 = {90: 63, 100: 64, 129: 127, 127: 127, 128: 64}
+
+
+def rotated_clique(n, k, hits, seed=59):
+    """A clique of n with k >= n colours whose value lists are rotations of the range: entity e's list starts at colour s_e <= e, the colours
+    s_e .. e - 1 are taken by the entities before it (entity i takes colour i), so its first strictly-improving candidate is colour e at
+    ordinal e - s_e.  `hits` fixes that ordinal for the named entities, the others get a seeded one."""
+    from solverforge_amd import datasets
+
+    r = datasets.stream(seed, n)
+    lists = []
+    for e in range(n):
+        s = e - hits[e] if e in hits else int(r[e] % np.uint64(e + 1))
+        lists.append([(s + j) % k for j in range(k)])
+    off, adj = _clique(n)
+    return _graph_case(f"rotated{n}x{k}", {"n": n, "n_colors": k, "adj_off": off, "adj": adj}, lists)
+
+
+WIDE_RETRY_ROWS = (70, 129)  # the rows the two rewards open: the second chunk, and the last ordinal of the ragged third
+
+
+def wide_retry_assignment(n=12):
+    """retry_assignment with 130 rows: the rewards open rows 70 and 129, every other cost is positive."""
+    import solverforge_amd as sfa
+
+    cost = np.full((n, WIDE), 2, dtype=np.int64)
+    cost[7, WIDE_RETRY_ROWS[0]], cost[9, WIDE_RETRY_ROWS[1]] = -1, -2
+    cost[3, :] = np.tile([1, 4, 1, 5], WIDE)[:WIDE]
+    row_w = np.ones(WIDE, dtype=np.int64)
+
+    def gpu(start, R, nullable):
+        assert nullable
+        return sfa.build_assignment(start, cost, WIDE, n_replicas=R, row_w=row_w, ex_level=0)
+
+    return Case("wideretry", n, WIDE, lambda sfo, start: sfo.Model.assignment(start, cost, WIDE, row_w=row_w, ex_level=0), gpu)
+
+
+def wide_retry_value_keys(heuristic):
+    """retry_value_keys for wide_retry_assignment: row 70 is the weakest value (heuristics 2, 3), or the first of the two strongest (70 and
+    129, in different chunks); under AllocateToValueFromQueue it sorts to ordinal 128."""
+    k = np.full(WIDE, 2, dtype=np.int64)
+    if heuristic in (2, 3):
+        k[:] = 3
+        k[WIDE_RETRY_ROWS[0]], k[100] = 0, 1
+    else:
+        k[0], k[71] = 0, 1
+        k[list(WIDE_RETRY_ROWS)] = 3
+    return k
+
+
+# ---- per-value tables wider than the wave -------------------------------------------------------------------------------------------------
+def table_keys(n_values, least, seed=61):
+    """Value keys with ties whose extreme -- the greatest key, or with least=True the least one -- occurs at values >= 64 only, first at
+    value 64: the strongest-fit heuristics take it with least=False, AllocateToValueFromQueue's ascending order starts with it with least=True."""
+    from solverforge_amd import datasets
+
+    r = datasets.stream(seed, n_values)
+    k = (r % np.uint64(2)).astype(np.int64)
+    k[64:] = (r[64:] % np.uint64(3)).astype(np.int64)
+    k[64] = 2
+    return -k if least else k
+
+
+def rotated_lists(n, n_values):
+    """Entity e's values are the range rotated to start at n_values - 1 - 3 e (mod n_values): first-fit picks start at the last value and
+    spread over the whole range."""
+    return [[(n_values - 1 - 3 * e + j) % n_values for j in range(n_values)] for e in range(n)]
+
+
+def wide_table_models():
+    """name -> a function (value_lists) -> Case: models whose per-value tables hold 65 to 130 values, with more entities than 64 so that the
+    constructed values reach indices >= 64.  12 * n_values is no multiple of 16 at 65, 70 and 130 values: the runs table of the shift models
+    starts at the aligned end of the count table, not at its end."""
+    models = {}
+    for bins in (65, 130):
+        for cap in (-1, 4, -2, -3):
+            models[f"balance{cap}x{bins}"] = lambda lists, bins=bins, cap=cap: _with_lists(balance(n=bins + 10, n_bins=bins, cap=cap, seed=7), lists)
+    models["assignment130"] = lambda lists: assignment(n=140, n_values=WIDE, seed=53, value_lists=lists)
+    for nurses in (65, 70):
+        models[f"shifts{nurses}"] = lambda lists, nurses=nurses: _with_lists(shift_schedule(n_nurses=nurses, n_days=40), lists)
+        models[f"presence{nurses}"] = lambda lists, nurses=nurses: _with_lists(shift_schedule(n_nurses=nurses, n_days=40, presence=(2, 9, 3)), lists)
+    return models
+
+
+def _with_lists(case, lists):
+    case.value_lists = lists
+    return case
+
+
+# ---- construction at a launch of several residencies --------------------------------------------------------------------------------------
+AT_SIZE_SEED, AT_SIZE_SEARCH_STEPS, AT_SIZE_SHIFT = 9_100, 18, 5
+
+
+def at_size_graph():
+    """40 vertices, 3 colours, dense: FirstFit leaves vertices unassigned."""
+    return graph(40, 180, 3, 13)
+
+
+def at_size_entity_keys():
+    return keys(40, 4, 67)
+
+
+def at_size_start(sfo, case, r):
+    """The start of replica r on the CPU: the all-unassigned model after AT_SIZE_SEARCH_STEPS steps of the scalar search seeded AT_SIZE_SEED + r."""
+    o = case.oracle(sfo)
+    o.configure(leaves=sfo.LEAF_SCALAR_CHANGE | sfo.LEAF_SCALAR_SWAP, random_seed=AT_SIZE_SEED + r)
+    o.phase_start()
+    o.steps(AT_SIZE_SEARCH_STEPS)
+    return o.get_vars(0, 0)
+
+
+# ---- the LDS gate of the per-value tables -------------------------------------------------------------------------------------------------
+def gate_starts(n_values, n=40):
+    """One head / reward value per entity, spread over the range: both ends, both sides of the first chunk boundary and of 64 KiB of tables."""
+    marks = [n_values - 1, 0, 64, n_values - 2, 63, min(5460, n_values - 3), n_values // 2, min(5459, n_values - 4)]
+    return [marks[e % len(marks)] for e in range(n)]
+
+
+def gate_balance(n_values, n=40):
+    """balance (the BalanceConstraint's statistic over the whole count table) whose value lists are rotations of the range: entities that
+    share a head push each other to the next bins, at both ends of the tables."""
+    heads = gate_starts(n_values, n)
+    lists = [np.roll(np.arange(n_values), -h).tolist() for h in heads]
+    return _with_lists(balance(n=n, n_bins=n_values, cap=-3, seed=7), lists)
+
+
+def gate_assignment(n_values, n=40):
+    """assignment with the exists node on the soft level: every cost is in 5..8 except one reward per entity (gate_starts) and a runner-up
+    next to it, so CheapestInsertion has to find its value among all the chunks of the placement."""
+    import solverforge_amd as sfa
+    from solverforge_amd import datasets
+
+    cost = (datasets.stream(73, n * n_values) % np.uint64(4)).astype(np.int64).reshape(n, n_values) + 5
+    for e, v in enumerate(gate_starts(n_values, n)):
+        cost[e, v] = -50 - e
+        cost[e, (v + 1) % n_values] = -40
+    row_w = (datasets.stream(74, n_values) % np.uint64(4)).astype(np.int64) + 1
+
+    def gpu(start, R, nullable):
+        assert nullable
+        return sfa.build_assignment(start, cost, n_values, n_replicas=R, row_w=row_w)
+
+    return Case(f"gateassign{n_values}", n, n_values, lambda sfo, start: sfo.Model.assignment(start, cost, n_values, row_w=row_w), gpu)

@@ -5,7 +5,9 @@
     the oracle Model's four primitives whose candidate value v scores v.
 The seven live-refresh heuristics and the value-candidate limit have no counterpart in the oracle: they are pinned to the mirror only
 (DESIGN §19); what is checked of them here is the mirror's own consistency -- incremental == fresh score, the counters' identities, and that
-the retry rule really fires."""
+the retry rule really fires.
+(c) The last section asserts, on the mirror / oracle alone, that every case of tests/test_gpu_scalar_construct_wide.py has the shape it
+    claims: which ordinal of a 130-candidate placement is taken, that values >= 64 are constructed, that the at-size starts are diverged."""
 import json
 import os
 
@@ -219,3 +221,166 @@ def test_construct_scalar_fails_loudly_without_device():
         assert _lib.ERRORS[rc] == "SF_ERR_INVALID"  # a device exists: the NULL context is the error
     else:
         assert _lib.ERRORS[rc] == "SF_ERR_NO_DEVICE"
+
+
+# ---- the shapes the wide GPU cases rest on (tests/test_gpu_scalar_construct_wide.py), on the mirror / oracle alone ------------------------
+BOTH = (mirror.PRESERVE_UNASSIGNED, mirror.ASSIGN_WHEN_CANDIDATE_EXISTS)
+STRENGTH = (mirror.WEAKEST_FIT, mirror.WEAKEST_FIT_DECREASING, mirror.STRONGEST_FIT, mirror.STRONGEST_FIT_DECREASING)
+LIMITS = (63, 64, 65, 129, 131)
+
+
+def _ordinals(case, vals):
+    """The ordinal of each assigned entity's value in its candidate list."""
+    return {e: (case.value_lists[e].index(int(v)) if case.value_lists is not None else int(v)) for e, v in enumerate(vals) if v >= 0}
+
+
+def test_wide_best_fit_takes_the_named_ordinals(oracle):
+    case = cases.best_fit_assignment(ex_level=-1)
+    for obligation in BOTH:
+        m = case.oracle(oracle)
+        st = mirror.construct(m, mirror.CHEAPEST_INSERTION, obligation=obligation, **_mirror_kwargs(case))
+        assert m.get_vars(0, 0)[:10].tolist() == [0, 63, 64, 65, 127, 128, 129, 10, 70, 0] == cases.BEST_FIT_VALUES
+        assert st["moves_generated"] == 3120 == st["score_calculations"] and st["step_count"] == 24 == st["moves_accepted"]
+
+
+def test_wide_best_fit_keeps_current_after_the_last_chunk(oracle):
+    """The exists node on the hard level: a row costs what the unassigned penalty gives back and every cost is positive, so the baseline is
+    strictly greater than the best of the 130 trials -- of the last chunk's too."""
+    case = cases.best_fit_assignment(ex_level=0)
+    m = case.oracle(oracle)
+    st = mirror.construct(m, mirror.CHEAPEST_INSERTION, **_mirror_kwargs(case))
+    assert st["kept"] >= 1 and st["candidates"][0] == 130 and st["placements"][0] == 0 and m.get_vars(0, 0)[0] == -1
+    assert st["score_calculations"] == 130 * st["step_count"]
+    forced = case.oracle(oracle)
+    st = mirror.construct(forced, mirror.CHEAPEST_INSERTION, obligation=mirror.ASSIGN_WHEN_CANDIDATE_EXISTS, **_mirror_kwargs(case))
+    assert forced.get_vars(0, 0)[0] == 0 and st["kept"] == 0  # entity 0 opens its best row
+
+
+@pytest.mark.parametrize("heuristic", STRENGTH)
+def test_wide_strength_extremes_sit_where_the_case_says(oracle, heuristic):
+    case = cases.wide_assignment()
+    ek = cases.keys(case.n, 4, 21)
+    for name, (vk, limit, want) in cases.strength_keys(heuristic in (mirror.WEAKEST_FIT, mirror.WEAKEST_FIT_DECREASING)).items():
+        for obligation in BOTH:
+            m = case.oracle(oracle)
+            st = mirror.construct(m, heuristic, obligation=obligation, value_candidate_limit=limit, entity_order_keys=ek, value_order_keys=vk, **_mirror_kwargs(case))
+            assert (m.get_vars(0, 0) == want).all(), (name, obligation)
+            assert st["moves_generated"] == case.n * (limit or 130)
+
+
+@pytest.mark.parametrize("heuristic", STRENGTH)
+def test_wide_lists_put_the_extreme_in_every_chunk(oracle, heuristic):
+    case = cases.wide_assignment(value_lists=cases.wide_lists(24))
+    assert sorted({len(l) for l in case.value_lists}) == cases.WIDE_LENGTHS and all(len(set(l)) == len(l) for l in case.value_lists)
+    m = case.oracle(oracle)
+    mirror.construct(m, heuristic, entity_order_keys=cases.keys(case.n, 4, 21), value_order_keys=cases.wide_list_keys(), **_mirror_kwargs(case))
+    vals = m.get_vars(0, 0)
+    assert (vals >= 0).all()
+    got = _ordinals(case, vals)
+    which = 2 if heuristic in (mirror.WEAKEST_FIT, mirror.WEAKEST_FIT_DECREASING) else 1
+    for e, placed in cases.WIDE_PLACED.items():
+        assert got[e] == placed[which], (e, got[e])
+    chosen = set(got.values())
+    assert any(k < 64 for k in chosen) and any(64 <= k < 128 for k in chosen) and any(k >= 128 for k in chosen)
+    assert chosen & {64, 128} and chosen & {127}  # lane 0 and lane 63 of a later chunk
+    assert len(chosen) >= 12  # the entities' extremes sit at different ordinals
+
+
+def test_wide_value_queue_never_passes_the_cut(oracle):
+    vk = cases.keys(cases.WIDE, 7, 71)
+    lists = cases.wide_lists(100)
+    for case in (cases.wide_clique(100), cases.wide_clique(100, value_lists=lists)):
+        deepest = 0
+        for limit in (0,) + LIMITS:
+            m = case.oracle(oracle)
+            st = mirror.construct(m, mirror.ALLOCATE_TO_VALUE_FROM_QUEUE, value_candidate_limit=limit, value_order_keys=vk, **_mirror_kwargs(case))
+            got = _ordinals(case, m.get_vars(0, 0))
+            assert all(k < (limit or 131) for k in got.values()), limit  # the cut comes before the sort
+            assert (m.score() == m.fresh_score()).all() and m.score()[0] == -st_unassigned(m)
+            if case.value_lists is None:
+                assert len(got) == min(limit or 130, 100)  # a clique: one colour each, and nothing beyond the cut
+            deepest = max(deepest, len(got))
+        assert deepest > 64  # the sorted order was walked past its first chunk: every taken colour lies before the one an entity takes
+
+
+def st_unassigned(m):
+    return int((m.get_vars(0, 0) < 0).sum())
+
+
+@pytest.mark.parametrize("n,k,hits", [(70, 80, cases.ROTATED_HITS_70), (130, 140, cases.ROTATED_HITS_130)])
+def test_rotated_lists_hit_at_the_named_ordinals(oracle, n, k, hits):
+    case = cases.rotated_clique(n, k, hits)
+    o = case.oracle(oracle)
+    o.construct_first_fit()
+    assert o.get_vars(0, 0).tolist() == list(range(n))  # entity e takes colour e ...
+    got = _ordinals(case, o.get_vars(0, 0))
+    assert all(got[e] == at for e, at in hits.items()) and {63, 64} <= set(hits.values())  # ... at the ordinal its rotation fixes
+    assert o.stats()["score_calculations"] == sum(k + 1 for k in got.values())
+    m = case.oracle(oracle)
+    st = mirror.construct(m, mirror.FIRST_FIT, **_mirror_kwargs(case))
+    assert (m.get_vars(0, 0) == o.get_vars(0, 0)).all() and st["score_calculations"] == o.stats()["score_calculations"]
+
+
+@pytest.mark.parametrize("heuristic", mirror.LIVE_REFRESH)
+def test_wide_live_refresh_retries_through_a_row_of_a_later_chunk(oracle, heuristic):
+    case = cases.wide_retry_assignment()
+    m = case.oracle(oracle)
+    st = mirror.construct(m, heuristic, entity_order_keys=cases.RETRY_ENTITY_KEYS, value_order_keys=cases.wide_retry_value_keys(heuristic), **_mirror_kwargs(case))
+    assert st["kept"] >= 1 and st["assigned_on_retry"] >= 1 and st["step_count"] > case.n
+    vals = m.get_vars(0, 0)
+    assert min(cases.WIDE_RETRY_ROWS) >= 64 and (vals[vals >= 0] >= 64).all() and (vals == cases.WIDE_RETRY_ROWS[0]).sum() > 1
+
+
+@pytest.mark.parametrize("name", list(cases.wide_table_models()))
+def test_wide_table_models_use_values_past_the_first_chunk(oracle, name):
+    """Every heuristic of the GPU test assigns values >= 64 on every model: scalar_tables_apply and the statistics of the balance models are
+    driven at table indices beyond the first round of lanes."""
+    make = cases.wide_table_models()[name]
+    case = make(None)
+    assert case.n > 64 and case.n_values >= 65 and (12 * case.n_values) % 16 != 0
+    ek = cases.keys(case.n, 4, 21)
+    for heuristic in (mirror.CHEAPEST_INSERTION, mirror.STRONGEST_FIT_DECREASING, mirror.ALLOCATE_TO_VALUE_FROM_QUEUE):
+        vk = cases.table_keys(case.n_values, least=heuristic == mirror.ALLOCATE_TO_VALUE_FROM_QUEUE)
+        for obligation in BOTH:
+            m = case.oracle(oracle)
+            mirror.construct(m, heuristic, obligation=obligation, entity_order_keys=ek, value_order_keys=vk, **_mirror_kwargs(case))
+            assert (m.score() == m.fresh_score()).all(), (heuristic, obligation)
+            # (fairness over the bins in use, cap -2: one bin is perfectly fair, so the best fit never opens a second one)
+            assert m.get_vars(0, 0).max() >= 64 or (heuristic == mirror.CHEAPEST_INSERTION and name.startswith("balance-2")), (heuristic, obligation)
+    listed = make(cases.rotated_lists(case.n, case.n_values))  # first fit takes the head of the list: the lists spread the heads over the range
+    o = listed.oracle(oracle)
+    o.construct_first_fit()
+    assert o.get_vars(0, 0).max() >= 64 and (o.score() == o.fresh_score()).all()
+    for obligation in BOTH:
+        m = listed.oracle(oracle)
+        mirror.construct(m, mirror.FIRST_FIT, obligation=obligation, **_mirror_kwargs(listed))
+        assert m.get_vars(0, 0).max() >= 64
+        if obligation == mirror.PRESERVE_UNASSIGNED:
+            assert (m.get_vars(0, 0) == o.get_vars(0, 0)).all()
+
+
+def test_at_size_starts_are_diverged_and_leave_work_to_the_kept_list(oracle):
+    """What the at-size GPU test rests on: the graph has the edges it claims, FirstFit leaves vertices unassigned, the searched starts of
+    different seeds differ and leave at least 10 vertices unassigned each, and at least half of the live-refresh runs keep entities and retry them."""
+    case = cases.at_size_graph()
+    o = case.oracle(oracle)
+    o.construct_first_fit()
+    assert (o.get_vars(0, 0) < 0).sum() >= 5
+    from solverforge_amd import datasets
+
+    g = datasets.make_graph(40, 180, 3, seed=13)
+    assert len(g["adj"]) == 2 * 180 and g["n_colors"] == 3
+    sample = [0, 1, 3, 4, 5, 63, 64, 16383, 16384, 16420, 8191, 8192]
+    starts = [cases.at_size_start(oracle, case, r) for r in sample]
+    assert len({tuple(s) for s in starts}) == len(starts) and all((s < 0).sum() >= 10 for s in starts) and all((s >= 0).any() for s in starts)
+    for heuristic in (mirror.FIRST_FIT_DECREASING, mirror.ALLOCATE_ENTITY_FROM_QUEUE):
+        fired = 0
+        for s in starts:
+            m = case.oracle(oracle, start=s)
+            st = mirror.construct(m, heuristic, entity_order_keys=cases.at_size_entity_keys(), **_mirror_kwargs(case))
+            assert (m.score() == m.fresh_score()).all()
+            # In graph colouring a kept vertex is never assigned later: every colour of it conflicts, and a construction only adds
+            # neighbours' colours.  What the kept list does here is to be retried, whole, after every later assignment.
+            assert st["assigned_on_retry"] == 0
+            fired += st["kept"] >= 1 and st["step_count"] > int((s < 0).sum())
+        assert 2 * fired >= len(starts), (heuristic, fired)
