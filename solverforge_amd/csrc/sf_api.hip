@@ -1109,24 +1109,24 @@ static int build_list_model(sf_ctx* ctx, int d) {
 
 // engine resolution: WAVE needs the neighbour index, u16-packable coordinates and an LDS slice per
 // replica small enough for several replicas per CU.
-static int list_max_nearby(sf_ctx* ctx) {
-    int mk = 1;
-    for (auto& s : ctx->selectors)
-        if (s.desc == ctx->list_desc && (s.kind == SF_SEL_NEARBY_LIST_CHANGE || s.kind == SF_SEL_NEARBY_LIST_SWAP) &&
-            s.max_nearby > mk)
-            mk = s.max_nearby;
-    return mk;
-}
-static bool wave_engine_possible(sf_ctx* ctx) {
+#include "sf_wave_plan.h"  // WaveShape / WaveKnobs / plan_wave_launch, wave_engine_fits / wave_engine_default: every decision about the wave launch
+
+// what the wave plan and engine resolution read of the context (launch_list_wave adds the launch's own parameters)
+static WaveShape wave_shape(const sf_ctx* ctx) {
+    WaveShape s{};
     const ListModel& m = ctx->lm;
-    // u16 element ids / ordinals in LDS; one wave's LDS slice must fit a CU
-    if (!ctx->nbr.keys || m.dim > 16384 || m.n_cap + m.V > 65535 || list_max_nearby(ctx) > 64) return false;
-    return WCarve(m.V, m.n_cap, m.dim, list_max_nearby(ctx)).total <= SF_LDS_BUDGET;
+    s.nbr_index = ctx->nbr.keys != nullptr, s.V = m.V, s.n_cap = m.n_cap, s.dim = m.dim, s.max_nearby = 1;
+    for (auto& sel : ctx->selectors)
+        if (sel.desc == ctx->list_desc && (sel.kind == SF_SEL_NEARBY_LIST_CHANGE || sel.kind == SF_SEL_NEARBY_LIST_SWAP) && sel.max_nearby > s.max_nearby)
+            s.max_nearby = sel.max_nearby;
+    s.levels = ctx->levels, s.mat32 = m.mat32 != nullptr, s.mat16 = m.mat16 != nullptr, s.small = ctx->lm_small, s.dist_level = m.dist_level;
+    return s;
 }
+static bool wave_engine_possible(sf_ctx* ctx) { return wave_engine_fits(wave_shape(ctx)); }
 static bool use_wave_engine(sf_ctx* ctx) {
     if (ctx->engine == SF_ENGINE_BLOCK) return false;
     if (ctx->engine == SF_ENGINE_WAVE) return true;  // validated in sf_solver_set_engine / launch
-    return wave_engine_possible(ctx) && WCarve(ctx->lm.V, ctx->lm.n_cap, ctx->lm.dim, list_max_nearby(ctx)).total <= SF_LDS_BUDGET / 2;
+    return wave_engine_default(wave_shape(ctx));
 }
 
 static int build_scalar_model(sf_ctx* ctx, int d);  // sf_api_scalar.inc
@@ -1218,85 +1218,20 @@ static int launch_list_search_t(sf_ctx* ctx, const SearchParams& p, int grid, bo
     HIPCHK(ctx, launch_tu_list_block<L>(trace, make_launch(ctx, &p, grid, 1024, lds)));
     return SF_OK;
 }
-template <int L>
-static int launch_list_wave_t(sf_ctx* ctx, const SearchParams& p, int n_replicas, bool trace) {
-    const bool fast = !trace && ctx->lm.mat32 && ctx->lm.dist_level >= 0 && p.acceptor == 1 && p.forager == 0 && !p.dry_run && p.n_leaves == 2 &&
-                      p.leaf[0].kind == SF_SEL_NEARBY_LIST_CHANGE && p.leaf[1].kind == SF_SEL_NEARBY_LIST_SWAP && p.order == SF_ORDER_RANDOM;
-    // replicas (waves) per workgroup: as many as the LDS holds, <= WPB; resident replicas per CU = whole workgroups in 160 KiB
-    auto plan = [&](bool compact, size_t wave_cap, int& wpb_out, size_t& lds_out, bool node_global = false) {
-        WCarve cvx(ctx->lm.V, ctx->lm.n_cap, ctx->lm.dim, list_max_nearby(ctx), compact, node_global);
-        size_t best = 0;
-        wpb_out = 1;
-        const char* wenv = std::getenv("SF_AMD_WAVE_WPB");  // diagnostics: cap the replicas per workgroup (A/B of the workgroup shape)
-        const int wmax = wenv && std::atoi(wenv) >= 1 && std::atoi(wenv) < WPB ? std::atoi(wenv) : WPB;
-        for (int w = 1; w <= wmax; ++w) {  // the workgroup size that keeps the most replicas resident (a workgroup's LDS is allocated whole)
-            const size_t per_wg = cvx.total * (size_t)w + (fast ? 0 : 1024);  // + the static annealing state (the FAST instantiations have none)
-            if (cvx.total * (size_t)w > SF_LDS_BUDGET) break;
-            size_t groups = (160 * 1024) / per_wg;
-            if (groups * (size_t)w > wave_cap) groups = wave_cap / (size_t)w;  // waves per CU by register budget
-            if (groups * (size_t)w >= best) {
-                best = groups * (size_t)w;
-                wpb_out = w;
-            }
-        }
-        lds_out = cvx.total * (size_t)wpb_out;
-        return best;
-    };
-    int wpb = 1;
-    size_t lds = 0;
-    const size_t resident_wide = plan(false, 4 * SF_WAVES_PER_EU, wpb, lds);
-    int mode = fast ? (ctx->lm_small ? 2 : 1) : 0;
-    if (mode == 2 && node_slot_compact_ok(ctx->lm.V) && ctx->lm.mat16) {  // (the COMPACT kernels gather from the u16 matrix)
-        // the COMPACT slice when it puts more replicas on a CU: CVRP-5000 5 instead of 3 (LDS-bound, compiled for 4 waves per SIMD);
-        // CVRP-1000 20 instead of 16 with the instantiation compiled for 5 waves per SIMD
-        static const bool no_compact = std::getenv("SF_AMD_NO_COMPACT") != nullptr;  // diagnostics: A/B
-        int wpb_c = 1;
-        size_t lds_c = 0;
-        static const int max_wpe = std::getenv("SF_AMD_WAVE_WPE") ? std::atoi(std::getenv("SF_AMD_WAVE_WPE")) : 6;  // diagnostics: cap the waves per SIMD (4 / 5 / 6)
-        const size_t r6 = (no_compact || max_wpe < 6) ? 0 : plan(true, 24, wpb_c, lds_c);
-        const size_t r5 = (no_compact || max_wpe < 5 || r6 > 20) ? 0 : plan(true, 20, wpb_c, lds_c);
-        if (r6 > 20 && r6 > resident_wide) {  // 24 replicas per CU: the instantiation compiled for 6 waves per SIMD (80 VGPRs)
-            mode = 5;
-            wpb = wpb_c;
-            lds = lds_c;
-        } else if (r5 > 16 && r5 > resident_wide) {
-            mode = 4;
-            wpb = wpb_c;
-            lds = lds_c;
-        } else if (!no_compact && plan(true, 4 * SF_WAVES_PER_EU, wpb_c, lds_c) > resident_wide) {
-            mode = 3;
-            wpb = wpb_c;
-            lds = lds_c;
-        }
-        // large models: the node -> slot table in HBM when that puts more replicas on a CU (a wave runs as fast at CVRP-5000 as at
-        // CVRP-1000; the slice decides how many are resident: 29 KB = 5 per CU, 19 KB = 8)
-        if (mode >= 3) {
-            const char* ng = std::getenv("SF_AMD_NODE_GLOBAL");  // diagnostics / parity tests: 0 = never, 1 = whenever the COMPACT slice is taken
-            const int ngv = ng ? std::atoi(ng) : -1;
-            int wpb_g = 1, wpb_3 = 1;
-            size_t lds_g = 0, lds_3 = 0;
-            const size_t r3 = plan(true, 4 * SF_WAVES_PER_EU, wpb_3, lds_3);
-            const size_t rg = plan(true, 4 * SF_WAVES_PER_EU, wpb_g, lds_g, true);
-            // (round 5 also carried a 64-register / 32-replicas-per-CU instantiation, launch mode 7: parity-green and 1.5 % SLOWER at CVRP-1000 --
-            // the scalar pipe is the bound, more waves do not help -- removed in round 6 with its untested code path)
-            if (ngv != 0 && (ngv == 1 || (mode == 3 && rg > r3))) {
-                if (!ctx->lm.node_tab) {
-                    uint16_t* nt = nullptr;
-                    int rc = dalloc(ctx, &nt, (size_t)ctx->R * ctx->lm.dim);
-                    if (rc) return rc;
-                    ctx->lm.node_tab = nt;
-                }
-                mode = 6;
-                wpb = wpb_g;
-                lds = lds_g;
-            }
-        }
-    }
+static int launch_list_wave(sf_ctx* ctx, const SearchParams& p, int n_replicas, bool trace) {
+    WaveShape s = wave_shape(ctx);
+    s.acceptor = p.acceptor, s.forager = p.forager, s.order = p.order, s.dry_run = p.dry_run, s.n_leaves = p.n_leaves;
+    for (int l = 0; l < p.n_leaves && l < MAX_LEAVES; ++l) s.kind[l] = p.leaf[l].kind;
+    s.n_replicas = n_replicas, s.trace = trace;
+    const WavePlan pl = plan_wave_launch(s, wave_knobs());
+    if (pl.err) return fail(ctx, pl.err, pl.msg);
+    if (pl.nodeg && !ctx->lm.node_tab)  // (a failed allocation leaves the pointer as it was)
+        if (int rc = dalloc(ctx, &ctx->lm.node_tab, (size_t)ctx->R * ctx->lm.dim)) return rc;
     SearchParams q = p;
     q.n_launch = n_replicas;
-    SearchLaunch la = make_launch(ctx, &q, (n_replicas + wpb - 1) / wpb, 64 * wpb, lds);
-    ctx->last_wave_mode = mode;
-    if (mode >= 3 && ctx->wave_renumbered) {  // the COMPACT kernels on the internal node numbering (ListModel::perm)
+    SearchLaunch la = make_launch(ctx, &q, pl.grid, pl.block, (size_t)pl.lds);
+    ctx->last_wave_mode = pl.mode;
+    if (pl.compact && ctx->wave_renumbered) {  // the COMPACT kernels on the internal node numbering (ListModel::perm)
         ctx->lm_wave = ctx->lm;
         ctx->lm_wave.perm = ctx->lm_wave_fix.perm, ctx->lm_wave.inv = ctx->lm_wave_fix.inv, ctx->lm_wave.mat16 = ctx->lm_wave_fix.mat16;
         if (ctx->lm.demand) ctx->lm_wave.demand = ctx->lm_wave_fix.demand;
@@ -1304,15 +1239,8 @@ static int launch_list_wave_t(sf_ctx* ctx, const SearchParams& p, int n_replicas
         la.lm = &ctx->lm_wave;
         la.nb = ctx->nbr_wave;
     }
-    HIPCHK(ctx, launch_tu_list_wave<L>(trace, mode, la));
+    HIPCHK(ctx, pl.levels == 2 ? launch_tu_list_wave<2>(trace, pl.mode, la) : launch_tu_list_wave<4>(trace, pl.mode, la));
     return SF_OK;
-}
-static int launch_list_wave(sf_ctx* ctx, const SearchParams& p, int grid, bool trace) {
-    if (!wave_engine_possible(ctx)) return fail(ctx, SF_ERR_UNSUPPORTED, "wave engine cannot run this model (needs a nearby matrix meter, <= 65535 elements, LDS slice <= 160 KiB)");
-    // kernels are instantiated for 2 and 4 score levels; 1- and 3-level models run with one padded
-    // (always zero) least-significant level, which never changes a lexicographic comparison
-    if (ctx->levels <= 2) return launch_list_wave_t<2>(ctx, p, grid, trace);
-    return launch_list_wave_t<4>(ctx, p, grid, trace);
 }
 static int launch_list_search(sf_ctx* ctx, const SearchParams& p, int grid, bool trace) {
     if (use_wave_engine(ctx)) return launch_list_wave(ctx, p, grid, trace);
@@ -2285,6 +2213,22 @@ extern "C" int32_t sf_debug_generic_plan(const int32_t* shape, int32_t n_shape, 
     const GenericPlan pl = plan_generic_launch(s, k);
     std::memcpy(plan, &pl, plan_bytes);
     if (msg) *msg = pl.msg;
+    return pl.err;
+}
+// The same for the wave engine (sf_wave_plan.h: WaveShape, WaveKnobs, WavePlan; tests/test_wave_plan.py).  `fits` (two words, when given)
+// receives wave_engine_fits and wave_engine_default of the shape: engine resolution.
+extern "C" int32_t sf_debug_wave_plan(const int32_t* shape, int32_t n_shape, const int32_t* knobs, int32_t n_knobs, int32_t* plan, int32_t n_plan, const char** msg, int32_t* fits) {
+    constexpr size_t plan_bytes = offsetof(WavePlan, msg);
+    if (!shape || !knobs || !plan || n_shape * 4 != (int)sizeof(WaveShape) || n_knobs * 4 != (int)sizeof(WaveKnobs) || n_plan * 4 != (int)plan_bytes)
+        return SF_ERR_INVALID;
+    WaveShape s;
+    WaveKnobs k;
+    std::memcpy(&s, shape, sizeof s);
+    std::memcpy(&k, knobs, sizeof k);
+    const WavePlan pl = plan_wave_launch(s, k);
+    std::memcpy(plan, &pl, plan_bytes);
+    if (msg) *msg = pl.msg;
+    if (fits) fits[0] = wave_engine_fits(s), fits[1] = wave_engine_default(s);
     return pl.err;
 }
 
