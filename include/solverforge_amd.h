@@ -756,6 +756,30 @@ int32_t sf_solver_configure_annealing(sf_ctx* ctx, const sf_annealing_config* cf
 int32_t sf_solver_configure_diversified(sf_ctx* ctx, double tolerance);
 /* acceptor state of one replica: current temperatures [score_levels] and whether it is still calibrating */
 int32_t sf_get_annealing_state(sf_ctx* ctx, int32_t replica, double* out_temperatures, int32_t* out_calibrating);
+/* Diagnostic: the SimulatedAnnealing acceptor alone, as the search engines run it (tests/test_gpu_anneal_chunks.py).  An engine
+ * decides 64 candidates of the pull order at once and then commits the acceptor state by the candidates the forager consumed; this
+ * entry point runs that pair on a scripted sequence of such chunks in one 64-lane launch, with the acceptor code of the engines
+ * and the state where they keep it.  The context gives device and stream only (no model needed); cfg, levels (1..SF_MAX_LEVELS) and
+ * hard_levels (0..levels) are those of this call, the initial state is that of sf_phase_start for replica 0.
+ * Per chunk: cur = the last step score, sc[lane] = the trial score of candidate `lane` (levels past `levels` are ignored), bit `lane`
+ * of doable = the candidate exists and is doable, nconsumed (0..64) = how many leading candidates the forager pulled, step_end != 0 =
+ * the step ends after this chunk.
+ * out_accept[c] = the accept decision of all 64 candidates of chunk c (those at or after nconsumed are speculative);
+ * out_state[c][0] = the state words after the commit, out_state[c][1] = after the step end (equal to [0] without one).
+ * State words: 0..3 rng (xoshiro256++), 4..7 temperatures (f64 bits), 8 calibrating, 9 samples seen, 10..13 samples per level,
+ * 14..17 / 18..21 low / high half of the per-level sample total; 9..21 stop moving when the calibration completes, the rest is
+ * scratch.  n_chunks <= SF_ANNEAL_DEBUG_MAX_CHUNKS. */
+#define SF_ANNEAL_STATE_WORDS 32
+#define SF_ANNEAL_DEBUG_MAX_CHUNKS 65536
+typedef struct sf_anneal_chunk {
+    int64_t cur[SF_MAX_LEVELS];
+    int64_t sc[64][SF_MAX_LEVELS];
+    uint64_t doable;
+    int32_t nconsumed;
+    int32_t step_end;
+} sf_anneal_chunk;
+int32_t sf_debug_anneal_chunks(sf_ctx* ctx, const sf_annealing_config* cfg, int32_t levels, int32_t hard_levels, int32_t n_chunks,
+                               const sf_anneal_chunk* chunks, uint64_t* out_accept, uint64_t* out_state);
 int32_t sf_solver_set_engine(sf_ctx* ctx, int32_t engine); /* sf_engine_kind; SF_ERR_UNSUPPORTED if it cannot run this model */
 int32_t sf_solver_get_engine(sf_ctx* ctx, int32_t* out_engine); /* the engine launches resolve to (after sf_initialize) */
 /* How the wave engine laid out its last fused launch (diagnostics; tests assert the path they mean to cover was taken):

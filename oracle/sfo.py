@@ -95,6 +95,12 @@ def lib():
             "sfo_model_evaluate_each": (i32, [vp, vp, vp, i32]),
             "sfo_model_configure_annealing": (None, [vp, i32, vp, i32, i32, dbl, dbl, i32, i32, dbl, dbl, u64]),
             "sfo_model_configure_diversified": (None, [vp, i32, dbl]),
+            "sfo_sa_create": (vp, [i32, vp, i32, i32, dbl, dbl, i32, i32, dbl, dbl, u64]),
+            "sfo_sa_destroy": (None, [vp]),
+            "sfo_sa_phase_started": (None, [vp]),
+            "sfo_sa_step_ended": (None, [vp]),
+            "sfo_sa_is_accepted": (None, [vp, vp, vp, i32, vp, vp, vp, vp]),
+            "sfo_sa_state": (None, [vp, vp, vp, vp, vp, vp, vp, vp]),
             "sfo_model_set_nearby_scalar": (None, [vp, i32, i32, vp, vp, vp, i32, i32, i64]),
             "sfo_model_annealing_state": (None, [vp, vp, vp, vp]),
             "sfo_xoshiro256pp": (None, [vp, i32, vp]),
@@ -529,6 +535,62 @@ class Model:
         vals = np.zeros(max_elements, dtype=np.uint32)
         t = lib().sfo_model_get_lists(self.h, desc, _p(off), _p(vals))
         return [list(map(int, vals[off[i]: off[i + 1]])) for i in range(n)]
+
+
+class Annealer:
+    """SimulatedAnnealingAcceptor without a Model: the parameters of Model.configure_annealing, then phase_started /
+    is_accepted / step_ended one call at a time and the whole acceptor state."""
+
+    def __init__(self, mode=2, temperatures=(), levels=2, hard_levels=1, decay_rate=0.999985,
+                 hill_climbing_temperature=1.0e-9, never_accept_hard=False, sample_size=128,
+                 target_probability=0.80, fallback_temperature=1.0, seed=0):
+        t = np.zeros(4, dtype=np.float64)
+        t[:len(temperatures)] = temperatures
+        self.h = C.c_void_p(lib().sfo_sa_create(mode, _p(t), levels, hard_levels, decay_rate, hill_climbing_temperature,
+                                                int(never_accept_hard), sample_size, target_probability,
+                                                fallback_temperature, seed))
+
+    def __del__(self):
+        try:
+            lib().sfo_sa_destroy(self.h)
+        except Exception:
+            pass
+
+    def phase_started(self):
+        lib().sfo_sa_phase_started(self.h)
+
+    def step_ended(self):
+        lib().sfo_sa_step_ended(self.h)
+
+    def is_accepted_many(self, last, moves):
+        """is_accepted(last, mv) for every row of moves [n, 4] in order: (accepted[n], drew[n], u[n], probability[n]);
+        u and probability are those of the Boltzmann test where drew is set."""
+        last = np.ascontiguousarray(last, dtype=np.int64)
+        moves = np.ascontiguousarray(moves, dtype=np.int64).reshape(-1, 4)
+        n = len(moves)
+        acc = np.zeros(n, dtype=np.int32)
+        drew = np.zeros(n, dtype=np.int32)
+        u = np.zeros(n, dtype=np.float64)
+        prob = np.zeros(n, dtype=np.float64)
+        if n:
+            lib().sfo_sa_is_accepted(self.h, _p(last), _p(moves), n, _p(acc), _p(drew), _p(u), _p(prob))
+        return acc.astype(bool), drew.astype(bool), u, prob
+
+    def is_accepted(self, last, move):
+        """(accepted, drew, u, probability) of one candidate."""
+        acc, drew, u, prob = self.is_accepted_many(last, np.asarray(move, dtype=np.int64).reshape(1, 4))
+        return bool(acc[0]), bool(drew[0]), float(u[0]), float(prob[0])
+
+    def state(self):
+        """dict: temperatures f64[4], rng u64[4], calibrating, samples_seen, count u64[4], total_lo / total_hi u64[4] (the
+        i128 total of the recorded samples per level)."""
+        t = np.zeros(4, dtype=np.float64)
+        r = np.zeros(4, dtype=np.uint64)
+        c = np.zeros(1, dtype=np.int32)
+        seen = np.zeros(1, dtype=np.uint64)
+        cnt, lo, hi = (np.zeros(4, dtype=np.uint64) for _ in range(3))
+        lib().sfo_sa_state(self.h, _p(t), _p(r), _p(c), _p(seen), _p(cnt), _p(lo), _p(hi))
+        return dict(temperatures=t, rng=r, calibrating=bool(c[0]), samples_seen=int(seen[0]), count=cnt, total_lo=lo, total_hi=hi)
 
 
 def compound_wire(candidates):

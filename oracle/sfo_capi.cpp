@@ -267,11 +267,10 @@ void sfo_model_configure(void* h, int32_t acceptor, int32_t la_size, int32_t for
 }
 // SimulatedAnnealingAcceptor (simulated_annealing.rs): mode 0 Single(temps[0]), 1 PerLevel(temps[0..levels]),
 // 2 Calibrated(sample_size, target, fallback).  Replaces the acceptor sfo_model_configure installed.
-void sfo_model_configure_annealing(void* h, int32_t mode, const double* temps, int32_t levels, int32_t hard_levels,
-                                   double decay_rate, double hill_climbing_temperature, int32_t never_accept_hard,
-                                   int32_t sample_size, double target_probability, double fallback_temperature,
-                                   uint64_t seed) {
-    Model* m = (Model*)h;
+static std::unique_ptr<SimulatedAnnealingAcceptor> make_annealing(int32_t mode, const double* temps, int32_t levels, int32_t hard_levels,
+                                                                  double decay_rate, double hill_climbing_temperature,
+                                                                  int32_t never_accept_hard, int32_t sample_size, double target_probability,
+                                                                  double fallback_temperature, uint64_t seed) {
     auto sa = std::make_unique<SimulatedAnnealingAcceptor>();
     sa->mode = (SimulatedAnnealingAcceptor::Mode)mode;
     sa->levels = levels;
@@ -285,7 +284,62 @@ void sfo_model_configure_annealing(void* h, int32_t mode, const double* temps, i
     sa->target_acceptance_probability = target_probability;
     sa->fallback_temperature = fallback_temperature;
     sa->rng = SmallRng::seed_from_u64(seed);
-    m->search.acceptor = std::move(sa);
+    return sa;
+}
+void sfo_model_configure_annealing(void* h, int32_t mode, const double* temps, int32_t levels, int32_t hard_levels,
+                                   double decay_rate, double hill_climbing_temperature, int32_t never_accept_hard,
+                                   int32_t sample_size, double target_probability, double fallback_temperature,
+                                   uint64_t seed) {
+    ((Model*)h)->search.acceptor = make_annealing(mode, temps, levels, hard_levels, decay_rate, hill_climbing_temperature, never_accept_hard,
+                                                  sample_size, target_probability, fallback_temperature, seed);
+}
+// The same acceptor without a Model (tests/anneal_chunk_cases.py drives it candidate by candidate).
+void* sfo_sa_create(int32_t mode, const double* temps, int32_t levels, int32_t hard_levels, double decay_rate,
+                    double hill_climbing_temperature, int32_t never_accept_hard, int32_t sample_size, double target_probability,
+                    double fallback_temperature, uint64_t seed) {
+    return make_annealing(mode, temps, levels, hard_levels, decay_rate, hill_climbing_temperature, never_accept_hard, sample_size,
+                          target_probability, fallback_temperature, seed)
+        .release();
+}
+void sfo_sa_destroy(void* h) { delete (SimulatedAnnealingAcceptor*)h; }
+void sfo_sa_phase_started(void* h) { ((SimulatedAnnealingAcceptor*)h)->phase_started(Score::zero()); }
+void sfo_sa_step_ended(void* h) { ((SimulatedAnnealingAcceptor*)h)->step_ended(Score::zero()); }
+// is_accepted(last, mv[i]) for i in 0..n, in order.  Per candidate: the flag, whether the Boltzmann test drew, and if so the
+// uniform draw and the acceptance probability it was compared with (0.0 otherwise).
+void sfo_sa_is_accepted(void* h, const int64_t* last4, const int64_t* mv4, int32_t n, int32_t* out_accepted, int32_t* out_drew,
+                        double* out_u, double* out_probability) {
+    auto* sa = (SimulatedAnnealingAcceptor*)h;
+    Score last;
+    for (int k = 0; k < MAX_LEVELS; ++k) last.v[k] = last4[k];
+    for (int32_t i = 0; i < n; ++i) {
+        Score mv;
+        for (int k = 0; k < MAX_LEVELS; ++k) mv.v[k] = mv4[(size_t)i * MAX_LEVELS + k];
+        out_accepted[i] = sa->is_accepted(last, mv) ? 1 : 0;
+        out_drew[i] = sa->last_drew ? 1 : 0;
+        out_u[i] = sa->last_drew ? sa->last_u : 0.0;
+        out_probability[i] = sa->last_drew ? sa->last_probability : 0.0;
+    }
+}
+// temperatures[4], rng state[4], calibrating flag, samples_seen, and per level the sample count and the exact i128 total of
+// the recorded samples as (low, high) 64-bit halves
+void sfo_sa_state(void* h, double* out_temps, uint64_t* out_rng, int32_t* out_calibrating, uint64_t* out_samples_seen,
+                  uint64_t* out_count, uint64_t* out_total_lo, uint64_t* out_total_hi) {
+    auto* sa = (SimulatedAnnealingAcceptor*)h;
+    for (int k = 0; k < MAX_LEVELS; ++k) out_temps[k] = (size_t)k < sa->current.size() ? sa->current[(size_t)k] : 0.0;
+    for (int i = 0; i < 4; ++i) out_rng[i] = sa->rng.s[i];
+    *out_calibrating = sa->calibrating ? 1 : 0;
+    *out_samples_seen = (uint64_t)sa->samples_seen;
+    for (int k = 0; k < MAX_LEVELS; ++k) {
+        __int128 total = 0;
+        size_t count = 0;
+        if ((size_t)k < sa->samples_by_level.size()) {
+            count = sa->samples_by_level[(size_t)k].size();
+            for (int64_t v : sa->samples_by_level[(size_t)k]) total += (__int128)v;
+        }
+        out_count[k] = (uint64_t)count;
+        out_total_lo[k] = (uint64_t)(unsigned __int128)total;
+        out_total_hi[k] = (uint64_t)((unsigned __int128)total >> 64);
+    }
 }
 // Nearby scalar sources of the model's scalar slot (scalar_access.rs:261-340) as data: which = 0 nearby VALUE candidates per
 // entity, 1 nearby ENTITY candidates per left entity; rows in source order (CSR), `dist` = the distance meter's value per row

@@ -147,6 +147,9 @@ struct SimulatedAnnealingAcceptor : Acceptor {
     bool calibrating = false;     // calibration_state.is_some()
     std::vector<std::vector<int64_t>> samples_by_level;
     size_t samples_seen = 0;
+    // what the last is_accepted did at the Boltzmann test (the stand-alone acceptor of sfo_capi.cpp reports it)
+    bool last_drew = false;
+    double last_u = 0.0, last_probability = 0.0;
 
     std::vector<double> calibrated_temperatures() const {  // CalibrationState::temperatures :72-87
         const double denominator = -std::log(target_acceptance_probability);
@@ -165,6 +168,7 @@ struct SimulatedAnnealingAcceptor : Acceptor {
     }
 
     bool is_accepted(const Score& last, const Score& mv) override {  // :338-375
+        last_drew = false;
         if (mv >= last) return true;
         int level = -1;
         for (int k = 0; k < levels; ++k)
@@ -187,7 +191,11 @@ struct SimulatedAnnealingAcceptor : Acceptor {
         const double temperature = current[(size_t)level];
         if (temperature <= hill_climbing_temperature) return false;
         const double probability = std::exp((double)delta / temperature);
-        return rng.random_f64() < probability;
+        const double u = rng.random_f64();
+        last_drew = true;
+        last_u = u;
+        last_probability = probability;
+        return u < probability;
     }
     void phase_started(const Score&) override {  // :377-415
         calibrating = false;

@@ -82,7 +82,9 @@ struct SaRng {
     }
 };
 
-// (hi:lo) as an unsigned 128-bit integer -> f64, round to nearest even (Rust `i128 as f64`, :81)
+// (hi:lo) as an unsigned 128-bit integer -> f64, round to nearest even (Rust `i128 as f64`, :81).
+// sh == 64 needs a total of 2^127 or more: every sample is below 2^63 and sample_size is an int32, so a total stays
+// below 2^94 and no run, and no test, reaches those two arms.  tests/anneal_chunk_cases.py covers sh = 1..7.
 __device__ __forceinline__ double sa_u128_to_f64(uint64_t hi, uint64_t lo) {
     if (hi == 0) return (double)lo;
     const int sh = 64 - __clzll((unsigned long long)hi);  // 1..64 bits above the low word

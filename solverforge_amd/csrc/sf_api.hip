@@ -1551,63 +1551,75 @@ int32_t sf_solver_configure_diversified(sf_ctx* ctx, double tolerance) {
     return SF_OK;
 }
 
-// assert_simulated_annealing_parameters (simulated_annealing.rs:305-336): the reference panics, the C ABI reports
-int32_t sf_solver_configure_annealing(sf_ctx* ctx, const sf_annealing_config* cfg) {
-    if (!ctx || !cfg) return SF_ERR_INVALID;
+// assert_simulated_annealing_parameters (simulated_annealing.rs:305-336) for a score of `levels` levels: nullptr, or what is wrong
+static const char* anneal_config_error(const sf_annealing_config* cfg, int levels) {
     auto temperature_ok = [](double v) { return std::isfinite(v) && v >= 0.0; };
-    if (cfg->mode < SF_ANNEAL_SINGLE || cfg->mode > SF_ANNEAL_CALIBRATED) return fail(ctx, SF_ERR_INVALID, "annealing mode");
+    if (cfg->mode < SF_ANNEAL_SINGLE || cfg->mode > SF_ANNEAL_CALIBRATED) return "annealing mode";
     if (!(std::isfinite(cfg->decay_rate) && cfg->decay_rate > 0.0 && cfg->decay_rate <= 1.0))
-        return fail(ctx, SF_ERR_INVALID, "simulated_annealing decay_rate must be finite and in (0, 1]");
+        return "simulated_annealing decay_rate must be finite and in (0, 1]";
     if (!temperature_ok(cfg->hill_climbing_temperature))
-        return fail(ctx, SF_ERR_INVALID, "simulated_annealing hill_climbing_temperature must be finite and non-negative");
-    const int nt = cfg->mode == SF_ANNEAL_SINGLE ? 1 : cfg->mode == SF_ANNEAL_PER_LEVEL ? ctx->levels : 0;
+        return "simulated_annealing hill_climbing_temperature must be finite and non-negative";
+    const int nt = cfg->mode == SF_ANNEAL_SINGLE ? 1 : cfg->mode == SF_ANNEAL_PER_LEVEL ? levels : 0;
     for (int k = 0; k < nt; ++k)
-        if (!temperature_ok(cfg->temperatures[k]))
-            return fail(ctx, SF_ERR_INVALID, "simulated_annealing level_temperatures must be finite and non-negative");
+        if (!temperature_ok(cfg->temperatures[k])) return "simulated_annealing level_temperatures must be finite and non-negative";
     if (cfg->mode == SF_ANNEAL_CALIBRATED) {
-        if (cfg->calibration_sample_size <= 0)
-            return fail(ctx, SF_ERR_INVALID, "simulated_annealing calibration sample_size must be greater than 0");
+        if (cfg->calibration_sample_size <= 0) return "simulated_annealing calibration sample_size must be greater than 0";
         if (!(std::isfinite(cfg->target_acceptance_probability) && cfg->target_acceptance_probability > 0.0 &&
               cfg->target_acceptance_probability < 1.0))
-            return fail(ctx, SF_ERR_INVALID, "simulated_annealing calibration target_acceptance_probability must be in (0, 1)");
+            return "simulated_annealing calibration target_acceptance_probability must be in (0, 1)";
         if (!temperature_ok(cfg->fallback_temperature))
-            return fail(ctx, SF_ERR_INVALID, "simulated_annealing calibration fallback_temperature must be finite and non-negative");
+            return "simulated_annealing calibration fallback_temperature must be finite and non-negative";
     }
+    return nullptr;
+}
+
+// the reference panics, the C ABI reports
+int32_t sf_solver_configure_annealing(sf_ctx* ctx, const sf_annealing_config* cfg) {
+    if (!ctx || !cfg) return SF_ERR_INVALID;
+    if (const char* why = anneal_config_error(cfg, ctx->levels)) return fail(ctx, SF_ERR_INVALID, why);
     ctx->anneal = *cfg;
     ctx->anneal_seed_set = true;
     return SF_OK;
 }
 
-// acceptor.phase_started (simulated_annealing.rs:377-415) for every replica; rng = SmallRng::seed_from_u64(seed + r)
+// the acceptor's parameters as the kernels take them; `state` stays the caller's
+static void anneal_params(const sf_annealing_config& a, int levels, int hard_levels, SaParams& sa) {
+    sa.decay_rate = a.decay_rate;
+    sa.hill_climbing_temperature = a.hill_climbing_temperature;
+    sa.denominator = -std::log(a.target_acceptance_probability);
+    sa.fallback_temperature = a.fallback_temperature;
+    sa.sample_size = a.calibration_sample_size > 0 ? a.calibration_sample_size : 1;
+    sa.never_accept_hard = a.never_accept_hard_regression;
+    sa.hard_levels = hard_levels;
+    sa.levels = levels;
+}
+
+// acceptor.phase_started (simulated_annealing.rs:377-415) for one replica into its SA_WORDS zeroed state words;
+// rng = SmallRng::seed_from_u64(seed)
+static void anneal_init_state(const sf_annealing_config& a, int levels, uint64_t seed, uint64_t* w) {
+    uint64_t state = seed;
+    for (int i = 0; i < 4; ++i) {  // xoshiro256++ seed_from_u64: splitmix64 expansion
+        state += 0x9E3779B97F4A7C15ULL;
+        uint64_t z = state;
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+        w[SA_RNG + i] = z ^ (z >> 31);
+    }
+    for (int k = 0; k < levels; ++k) {
+        double t = a.mode == SF_ANNEAL_SINGLE ? a.temperatures[0] : a.mode == SF_ANNEAL_PER_LEVEL ? a.temperatures[k] : 0.0;
+        std::memcpy(&w[SA_TEMP + k], &t, 8);
+    }
+    w[SA_CALIBRATING] = a.mode == SF_ANNEAL_CALIBRATED ? 1 : 0;
+}
+
+// phase_started for every replica; replica r is seeded with seed + r
 static int anneal_phase_start(sf_ctx* ctx) {
     const sf_annealing_config& a = ctx->anneal;
     SearchParams& p = ctx->sp;
-    p.sa.decay_rate = a.decay_rate;
-    p.sa.hill_climbing_temperature = a.hill_climbing_temperature;
-    p.sa.denominator = -std::log(a.target_acceptance_probability);
-    p.sa.fallback_temperature = a.fallback_temperature;
-    p.sa.sample_size = a.calibration_sample_size > 0 ? a.calibration_sample_size : 1;
-    p.sa.never_accept_hard = a.never_accept_hard_regression;
-    p.sa.hard_levels = ctx->hard_levels;
-    p.sa.levels = ctx->levels;
+    anneal_params(a, ctx->levels, ctx->hard_levels, p.sa);
     const uint64_t seed = ctx->anneal_seed_set ? a.seed : ctx->cfg.random_seed;
     std::vector<uint64_t> st((size_t)ctx->R * SA_WORDS, 0);
-    for (int r = 0; r < ctx->R; ++r) {
-        uint64_t* w = st.data() + (size_t)r * SA_WORDS;
-        uint64_t state = seed + (uint64_t)r;
-        for (int i = 0; i < 4; ++i) {  // xoshiro256++ seed_from_u64: splitmix64 expansion
-            state += 0x9E3779B97F4A7C15ULL;
-            uint64_t z = state;
-            z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-            z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-            w[SA_RNG + i] = z ^ (z >> 31);
-        }
-        for (int k = 0; k < ctx->levels; ++k) {
-            double t = a.mode == SF_ANNEAL_SINGLE ? a.temperatures[0] : a.mode == SF_ANNEAL_PER_LEVEL ? a.temperatures[k] : 0.0;
-            std::memcpy(&w[SA_TEMP + k], &t, 8);
-        }
-        w[SA_CALIBRATING] = a.mode == SF_ANNEAL_CALIBRATED ? 1 : 0;
-    }
+    for (int r = 0; r < ctx->R; ++r) anneal_init_state(a, ctx->levels, seed + (uint64_t)r, st.data() + (size_t)r * SA_WORDS);
     HIPCHK(ctx, hipMemcpyAsync(p.sa.state, st.data(), st.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return SF_OK;
@@ -2253,3 +2265,4 @@ extern "C" int32_t sf_debug_phases(uint64_t* out8) {  // diagnostic builds only 
 #include "sf_api_scalar_construct.inc"
 #include "sf_portfolio.inc"
 #include "sf_candidate_trace.inc"
+#include "sf_api_anneal_debug.inc"

@@ -12,7 +12,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import (MOVE_DTYPE, AnnealingConfigStruct, ScalarConstructionConfigStruct, SolverConfigStruct, SolverForgeError, StatsStruct,
+from ._lib import (ANNEAL_CHUNK_DTYPE, ANNEAL_STATE_WORDS, MOVE_DTYPE, AnnealingConfigStruct, ScalarConstructionConfigStruct, SolverConfigStruct, SolverForgeError, StatsStruct,
                    check, ptr)
 
 
@@ -571,6 +571,22 @@ class GpuScoreDirector:
         s = AnnealingConfigStruct(mode, int(never_accept_hard_regression), calibration_sample_size, 0, t, decay_rate,
                                   hill_climbing_temperature, target_acceptance_probability, fallback_temperature, seed)
         check(self._L.sf_solver_configure_annealing(self._h, C.byref(s)), self._h)
+
+    def debug_anneal_chunks(self, chunks, levels=2, hard_levels=1, mode=AnnealingMode.CALIBRATED, temperatures=(), decay_rate=0.999985,
+                            hill_climbing_temperature=1.0e-9, never_accept_hard_regression=False, calibration_sample_size=128,
+                            target_acceptance_probability=0.80, fallback_temperature=1.0, seed=0):
+        """sf_debug_anneal_chunks: the engines' acceptor alone on a scripted sequence.  chunks: array of ANNEAL_CHUNK_DTYPE (cur[4],
+        sc[64][4], doable mask, nconsumed, step_end).  Returns (accept masks u64[n], state words u64[n, 2, 32]: after the commit and
+        after the step end).  The context's own model and configuration play no part."""
+        chunks = np.ascontiguousarray(chunks, dtype=ANNEAL_CHUNK_DTYPE)
+        n = len(chunks)
+        t = (C.c_double * 4)(*([float(x) for x in temperatures] + [0.0] * (4 - len(temperatures))))
+        s = AnnealingConfigStruct(mode, int(never_accept_hard_regression), calibration_sample_size, 0, t, decay_rate,
+                                  hill_climbing_temperature, target_acceptance_probability, fallback_temperature, seed)
+        accept = np.zeros(max(n, 1), dtype=np.uint64)
+        state = np.zeros((max(n, 1), 2, ANNEAL_STATE_WORDS), dtype=np.uint64)
+        check(self._L.sf_debug_anneal_chunks(self._h, C.byref(s), levels, hard_levels, n, ptr(chunks), ptr(accept), ptr(state)), self._h)
+        return accept[:n], state[:n]
 
     def configure_diversified(self, tolerance=0.01):
         """Tolerance of AcceptorKind.DIVERSIFIED_LATE_ACCEPTANCE (DiversifiedLateAcceptanceAcceptor::new); the history size

@@ -1,8 +1,12 @@
 """GPU parity tests (through the C ABI): SimulatedAnnealing acceptor on every search engine vs the
 CPU oracle (phase/localsearch/acceptor/simulated_annealing.rs).  Candidate order, trial scores,
-accept flags, applied moves, counters and the f64 temperatures must agree exactly; the Boltzmann
-test itself uses the device exp(), which may differ from glibc by one ulp -- a flag could only
-differ if a draw landed within one ulp of the acceptance probability (never observed)."""
+accept flags, applied moves, counters and the f64 temperatures must agree exactly.
+
+The tie rule: the Boltzmann test uses the device exp(), which may differ from glibc's by one ulp, so a draw with
+|u - probability| <= 4 * spacing(probability) is undecidable, and only at such a draw might a flag differ.  The scripted
+sequences of tests/anneal_chunk_cases.py are proven free of such draws on the oracle alone (tests/test_anneal_chunk_cases.py)
+and compared flag by flag on the device (tests/test_gpu_anneal_chunks.py); the runs here are whole searches, where one
+differing flag changes every later candidate and fails the comparison at that step."""
 import numpy as np
 import pytest
 
@@ -48,7 +52,9 @@ def _compare_state(d, o, levels=2):
     assert (gt.view(np.uint64) == ot[:levels].view(np.uint64)).all(), (gt, ot)
 
 
-def _traced(d, o, steps, levels=2):
+def _traced(d, o, steps, levels=2, worse_levels=None, states=None):
+    """worse_levels: a list that receives the first differing level of every accepted worsening candidate; states: a list that
+    receives the oracle's (temperatures, calibrating) after every step."""
     d.calculate_score()
     d.phase_start()
     o.phase_start()
@@ -67,7 +73,12 @@ def _traced(d, o, steps, levels=2):
         for sc, fl in zip(os_[:, :levels], of):
             if fl & 2 and tuple(sc) < tuple(last):
                 accepted_worse += 1
+                if worse_levels is not None:
+                    worse_levels.append(int(np.flatnonzero(sc != last)[0]))
         _compare_state(d, o, levels)
+        if states is not None:
+            ot, _, oc = o.annealing_state()
+            states.append((ot[:levels].copy(), bool(oc)))
     assert (d.calculate_score()[0] == o.score()[:levels]).all()
     assert (d.best_scores()[0] == o.best_score()[:levels]).all()
     gst, ost = d.stats(0), o.stats()
@@ -158,6 +169,95 @@ def test_generic_engine_annealing_traced_steps(oracle):
     bits = oracle.LEAF_NEARBY_LIST_CHANGE | oracle.LEAF_LIST_SWAP | oracle.LEAF_LIST_REVERSE
     _configure(d, o, oracle, bits, 0, 5, 31, dict(mode=2, sample_size=20), max_nearby=8)
     assert _traced(d, o, 50) > 0
+
+
+def test_large_magnitude_annealing_scalar_engine(oracle):
+    """58-bit costs: the calibration's level-1 total passes 2^64 (the high word of the 128-bit sum, its conversion to f64), and
+    delta / T runs on 58-bit deltas against a temperature near 2^60.  Scalar engine, calibrated over 512 samples."""
+    import solverforge_amd as sfa
+    from solverforge_amd import datasets
+
+    n, k = 16, 8
+    r = datasets.stream(3, n + n * k)
+    values = (r[:n] % np.uint64(k)).astype(np.int64)
+    cost = ((r[n:] >> np.uint64(6)) | np.uint64(1)).astype(np.int64).reshape(n, k)
+    assert int(cost.max()).bit_length() == 58
+    d = sfa.build_assignment(values, cost, k, ex_level=-1, cost_weight=1)
+    o = oracle.Model.assignment(values, cost, k, ex_level=-1, cost_weight=1)
+    _configure(d, o, oracle, oracle.LEAF_SCALAR_CHANGE | oracle.LEAF_SCALAR_SWAP, 0, 1, 3, dict(mode=2, sample_size=512))
+    states = []
+    worse = _traced(d, o, 60, states=states)
+    done = [i for i, (_, calibrating) in enumerate(states) if not calibrating]
+    assert done and 0 < done[0] < 59  # steps on both sides of the completion were traced
+    t_done = states[done[0]][0]  # after that step's own cooling: a little below the installed temperature
+    assert t_done[1] * -np.log(0.8) * 512 > 2 ** 64  # mean = T * -ln(p): the level-1 total had a non-zero high word
+    assert worse > 0
+    d.solve_steps(340)  # a fused window behind the traced steps
+    o.steps(340)
+    assert (d.working_values(0, 0, replica=0) == o.get_vars(0, 0)).all()
+    assert (d.calculate_score()[0] == o.score()[:2]).all() and (d.best_scores()[0] == o.best_score()[:2]).all()
+    _compare_state(d, o)
+    gst, ost = d.stats(0), o.stats()
+    for key in ["step_count", "moves_evaluated", "moves_accepted", "moves_applied", "score_calculations"]:
+        assert gst[key] == ost[key], key
+    model, gen = d.arith_flags()
+    assert model["scalar_value_bytes"] != 0 and gen is None, (model, gen)  # the scalar engine ran, the generic one never
+
+
+@pytest.mark.parametrize("anneal,limit", [
+    (dict(mode=2, sample_size=40), 8),
+    (dict(mode=1, temperatures=(0.7, 3.0, 25.0), decay_rate=0.99), 4),
+    (dict(mode=1, temperatures=(50.0, 50.0, 50.0), never_accept_hard=True), 16),
+])
+def test_three_level_annealing_generic_engine(oracle, anneal, limit):
+    """The four-level build of the acceptor inside an engine: three score levels, two of them hard, three temperatures cooling.
+    Every worsening candidate this model accepts differs first at level index 2 (no hard-level draw happens on it even at
+    T = 6); hard-level draws of the four-level build are the harness's job (tests/test_gpu_anneal_chunks.py)."""
+    import solverforge_amd as sfa
+
+    from test_gpu_large_launch import _JobShop
+
+    p = _JobShop()._problem()  # the 12 x 5 mixed job shop: BendableScore<2, 1>, four leaves
+    d = sfa.build_jobshop(p, n_replicas=1, bendable=True)
+    o = oracle.Model.jobshop(p["job"], p["machine_idx"], p["sequences"], bendable=True)
+    bits = oracle.LEAF_LIST_CHANGE | oracle.LEAF_LIST_SWAP | oracle.LEAF_SCALAR_CHANGE | oracle.LEAF_SCALAR_SWAP
+    _configure(d, o, oracle, bits, 0, limit, 13, anneal, levels=3, hard_levels=2)
+    levels = []
+    assert _traced(d, o, 80, levels=3, worse_levels=levels) > 0
+    assert set(levels) == {2}
+    _, gen = d.arith_flags()
+    assert gen is not None and gen["levels"] == 4, gen
+
+
+def test_three_level_annealing_scalar_engine(oracle):
+    """The scalar engine's four-level build: an assignment on three levels (unassigned / cost / rows in use), costs in 0..2 so
+    that candidates differ first at level 2 as well."""
+    from solverforge_amd.director import ConstraintKind, GpuScoreDirector, SelectorKind
+    from solverforge_amd import datasets
+    from solverforge_amd.models import FACT_COLUMN, FACT_MATRIX
+
+    n, k = 12, 8
+    r = datasets.stream(21, n + n * k + k)
+    values = (r[:n] % np.uint64(k + 1)).astype(np.int64) - 1
+    cost = (r[n:n + n * k] % np.uint64(3)).astype(np.int64).reshape(n, k)
+    row_w = (r[n + n * k:] % np.uint64(9)).astype(np.int64) + 1
+    d = GpuScoreDirector(score_levels=3, hard_levels=1, n_replicas=1)
+    d.add_entity_class(0, n)
+    d.add_scalar_variable(0, 0, k, True, values)
+    d.add_fact_matrix(FACT_MATRIX, cost)
+    d.add_fact_column_i32(FACT_COLUMN, row_w.astype(np.int32))
+    d.add_constraint(ConstraintKind.UNI_UNASSIGNED, 0, level=0, weight=1)
+    d.add_constraint(ConstraintKind.VALUE_COST, 0, fact=FACT_MATRIX, level=1, weight=1)
+    d.add_constraint(ConstraintKind.EXISTS_VALUE, 0, fact=FACT_COLUMN, param=1, level=2, weight=3)
+    d.add_selector(SelectorKind.SCALAR_CHANGE, 0)
+    d.add_selector(SelectorKind.SCALAR_SWAP, 0)
+    o = oracle.Model.assignment(values, cost, k, row_w=row_w, ex_mode=1, ex_level=2, ex_weight=3)
+    _configure(d, o, oracle, oracle.LEAF_SCALAR_CHANGE | oracle.LEAF_SCALAR_SWAP, 0, 4, 19, dict(mode=2, sample_size=30), levels=3, hard_levels=1)
+    levels = []
+    assert _traced(d, o, 100, levels=3, worse_levels=levels) > 0
+    assert {1, 2} <= set(levels)
+    model, gen = d.arith_flags()
+    assert model["scalar_value_bytes"] != 0 and gen is None, (model, gen)
 
 
 def test_annealing_parameter_validation():
