@@ -2244,6 +2244,18 @@ extern "C" int32_t sf_debug_wave_plan(const int32_t* shape, int32_t n_shape, con
     return pl.err;
 }
 
+// The order tables' 32-bit Barrett index (sf_common.h: perm_index_recip) on the host, for tests/test_wave_step_arith.py: no device, no context.
+//   what = 0: out[i] = perm_index_recip(start, stride, k[i], V, floor(2^32 / V))       V = 2 .. 1022, the reciprocal as the kernel forms it
+//   what = 1: out[i] = fastmod_u64(start + k[i] x stride, make_fastmod(V))             the form it replaces, same arguments
+extern "C" int32_t sf_debug_step_arith(int32_t what, uint32_t start, uint32_t stride, uint32_t V, const uint32_t* k, int64_t n_k, uint32_t* out) {
+    if (!k || !out || n_k < 0 || V < 2 || V > 1022 || (what != 0 && what != 1)) return SF_ERR_INVALID;
+    const uint32_t rc = (uint32_t)(0x100000000ull / V);  // k_list_search_wave's v_recip32
+    const FastMod fm = make_fastmod(V);
+    for (int64_t i = 0; i < n_k; ++i)
+        out[i] = what == 0 ? perm_index_recip(start, stride, k[i], V, rc) : fastmod_u64((uint64_t)start + (uint64_t)k[i] * stride, fm);
+    return SF_OK;
+}
+
 #ifdef SF_PHASE_PROFILE
 extern "C" int32_t sf_debug_ruin_phases(uint64_t* out8) {  // diagnostic builds only: shader clocks inside ruin_recreate
     if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(sf::g_rphase), 64) != hipSuccess) return SF_ERR_HIP;

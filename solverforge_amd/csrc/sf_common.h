@@ -112,6 +112,25 @@ SF_HD uint32_t fastmod_u64(uint64_t x, const FastMod& f) {
     return r;
 }
 
+// 32-bit Barrett remainder by a divisor n >= 2 whose reciprocal floor(2^32 / n) the caller keeps.  For ANY 32-bit x the quotient estimate
+// hi32(x * recip) is floor(x / n) or one short (x * recip / 2^32 > x / n - x / 2^32 > x / n - 1), so one conditional subtraction finishes it.
+SF_HD uint32_t mulhi32(uint32_t a, uint32_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __umulhi(a, b);
+#else
+    return (uint32_t)(((uint64_t)a * b) >> 32);
+#endif
+}
+SF_HD uint32_t mod_u32_recip(uint32_t x, uint32_t n, uint32_t recip) {
+    const uint32_t r = x - mulhi32(x, recip) * n;
+    return r >= n ? r - n : r;
+}
+// The order tables' index (start + k x stride) mod V as one such step: start, stride and k are below V <= 1022 in the layouts that use it, so
+// the argument stays below 2^21.  What fastmod_u64 gives for the same arguments (tests/test_wave_step_arith.py), without its 64 x 64 high multiply.
+SF_HD uint32_t perm_index_recip(uint32_t start, uint32_t stride, uint32_t k, uint32_t V, uint32_t recip) {
+    return mod_u32_recip(start + k * stride, V, recip);
+}
+
 SF_HD int ctz_u64(uint64_t v) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __ffsll((unsigned long long)v) - 1;

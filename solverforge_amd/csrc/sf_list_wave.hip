@@ -297,11 +297,14 @@ __device__ __forceinline__ uint32_t mbcnt64(uint64_t mask) {
 }
 
 // Committed move application on the wave's LDS state (ListChange / ListSwap do_move).
-template <class LT, class OT>  // LT = the replica's per-list load type in LDS: int64_t, or int32_t in the COMPACT wave layout; OT = offsets, uint32_t or uint16_t
+// OWN_LANE: the lane index is formed again here, behind an empty asm -- for a caller with no vector register to spare, whose compiler would otherwise
+// compute this block's per-lane addresses in the kernel's prologue and carry them to it through scratch memory
+template <class LT, class OT, bool OWN_LANE = false>  // LT = the replica's per-list load type in LDS: int64_t, or int32_t in the COMPACT wave layout; OT = offsets, uint32_t or uint16_t
 __device__ __forceinline__ void apply_list_move_wave(const ListModel& m, uint16_t* visits, OT* off,
                                                      LT* load, int kind, uint32_t a, uint32_t i, uint32_t b,
                                                      uint32_t j, uint32_t ext = 0) {
-    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t lane = threadIdx.x & 63u;
+    if constexpr (OWN_LANE) asm volatile("" : "+v"(lane));
     if (kind == 2) {
         const uint32_t P = off[a] + i, Q = off[b] + j;
         const uint32_t x = visits[P];
@@ -1204,11 +1207,13 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
             for (uint32_t base = 0; base < (uint32_t)V; base += 64) {
                 const uint32_t k = base + lane;
                 if constexpr (RANKTAB) {  // the rank alone: no list lengths, no prefix scan
-                    if (k < (uint32_t)V) rt[fastmod_u64((uint64_t)pst + (uint64_t)k * psd, fm_V)] = k;
+                    // start + k x stride < V^2 + V < 2^21 (V <= 1022, node_slot_compact_ok): resolve()'s 32-bit Barrett step, not the 64 x 64 high
+                    // multiply of fastmod_u64 (quarter-rate multiplies, two table chunks per leaf and step at 100 lists)
+                    if (k < (uint32_t)V) rt[perm_index_recip(pst, psd, k, (uint32_t)V, v_recip32)] = k;
                 } else {
                     uint32_t v = 0, e = 0;
                     if (k < (uint32_t)V) {
-                        e = fastmod_u64((uint64_t)pst + (uint64_t)k * psd, fm_V);
+                        e = fastmod_u64((uint64_t)pst + (uint64_t)k * psd, fm_V);  // (the wide layouts only: every COMPACT kernel is RANKTAB above or, NODEG, has left the loop at ARANK)
                         if constexpr (!COMPACT) ra[k] = (uint16_t)e;
                         v = s_off[e + 1] - s_off[e] + 1;
                     }
@@ -1857,8 +1862,13 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                     const uint32_t tot = uni(s_off[V]);
                     uint32_t* const bv = SF_COLD_M(best_visits) + (size_t)r * SF_COLD_M(n_cap);
                     uint32_t* const bo = SF_COLD_M(best_off) + (size_t)r * (V + 1);
-                    for (uint32_t t = lane; t < tot; t += 64) bv[t] = ext_id(s_visits[t]);
-                    for (uint32_t t = lane; t <= (uint32_t)V; t += 64) bo[t] = s_off[t];
+                    // RANKTAB: the lane index is formed again HERE.  Taken from the kernel's `lane`, this cold block's per-lane LDS and global
+                    // addresses are computed in the kernel's prologue and carried to it -- the kernel has no free vector register, so with the
+                    // table index above they went through scratch memory
+                    uint32_t ln = lane;
+                    if constexpr (RANKTAB) asm volatile("" : "+v"(ln));
+                    for (uint32_t t = ln; t < tot; t += 64) bv[t] = ext_id(s_visits[t]);
+                    for (uint32_t t = ln; t <= (uint32_t)V; t += 64) bo[t] = s_off[t];
                     best_pending = false;
                 }
             }
@@ -1883,7 +1893,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                 }
                 nsat = uni(nsat);  // (the move's kind comes out of a shuffle: say that the count is wave-uniform, so the pass branches on a scalar)
             }
-            apply_list_move_wave(m, s_visits, s_off, s_load, kind, a, i, b, j);
+            apply_list_move_wave<LT, OT, RANKTAB && L == 4>(m, s_visits, s_off, s_load, kind, a, i, b, j);  // (the four-level COMPACT kernels: one register short without it)
             {  // refresh node -> (route, position) for the two touched routes
                 const uint32_t oa = s_off[a], la = s_off[a + 1] - oa;
                 const uint32_t ob = s_off[b], lb = s_off[b + 1] - ob;
