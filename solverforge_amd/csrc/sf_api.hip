@@ -119,6 +119,8 @@ struct sf_ctx {
     NbrIndex nbr_wave{nullptr};   // ... and its neighbour index
     bool wave_renumbered = false;
     int last_wave_mode = -1;      // launch mode of the last wave-engine launch (sf_list_wave_layout)
+    int32_t wave_spec_state = 0, wave_spec_reason = 0, wave_spec_key[18] = {};  // ... and whether it ran the kernel compiled for this context's constants (sf_debug_wave_spec)
+    int n_cus = 0;                // CUs of the device (read at the first wave launch)
     int32_t last_generic_flags = -1;  // what the last generic-engine launch took (sf_list_arith_flags)
     int32_t last_scalar_value_bytes = 0;  // value-type bytes of the last scalar-engine launch (sf_list_arith_flags)
     int xown_level = -1;             // SF_C_CROSS_OWNER_MATCH of a mixed model: level / weight / the [R][n_scalar] entity -> holding list map
@@ -1110,6 +1112,7 @@ static int build_list_model(sf_ctx* ctx, int d) {
 // engine resolution: WAVE needs the neighbour index, u16-packable coordinates and an LDS slice per
 // replica small enough for several replicas per CU.
 #include "sf_wave_plan.h"  // WaveShape / WaveKnobs / plan_wave_launch, wave_engine_fits / wave_engine_default: every decision about the wave launch
+#include "sf_wave_spec.h"  // WaveSpecKey / WaveSpecGate / wave_spec_wanted / wave_spec_get: the kernel compiled at run time for the context's constants
 
 // what the wave plan and engine resolution read of the context (launch_list_wave adds the launch's own parameters)
 static WaveShape wave_shape(const sf_ctx* ctx) {
@@ -1238,6 +1241,24 @@ static int launch_list_wave(sf_ctx* ctx, const SearchParams& p, int n_replicas, 
         ctx->lm_wave.depot = ctx->lm_wave_fix.depot;
         la.lm = &ctx->lm_wave;
         la.nb = ctx->nbr_wave;
+    }
+    // the kernel compiled for this context's constants, when the policy wants it and it can be had; else the ahead-of-time one
+    if (!ctx->n_cus) HIPCHK(ctx, hipDeviceGetAttribute(&ctx->n_cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    const WaveSpecGate gate{pl.mode, q.move_budget != 0, (int32_t)std::min<int64_t>(std::max<int64_t>(q.n_steps, 0), INT32_MAX), n_replicas, pl.resident, ctx->n_cus, wave_spec_knob()};
+    const WaveSpecKey key = wave_spec_key(pl.levels, pl.wpe, *la.lm, q, wave_spec_extras());
+    ctx->wave_spec_state = SF_WSPEC_AOT, ctx->wave_spec_reason = wave_spec_wanted(gate);
+    std::memcpy(ctx->wave_spec_key, &key, sizeof key);
+    if (ctx->wave_spec_reason == SF_WSPEC_R_NONE) {
+        hipFunction_t fn = nullptr;
+        if ((ctx->wave_spec_reason = wave_spec_get(key, ctx->device, la.lds, &fn)) == SF_WSPEC_R_NONE) {
+            WaveArgs args{*la.lm, q, la.nb};  // the kernel's argument block as it lies in the kernarg segment (sf_list_wave.hip)
+            size_t n_args = sizeof args;
+            void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &n_args, HIP_LAUNCH_PARAM_END};
+            HIPCHK(ctx, hipModuleLaunchKernel(fn, (unsigned)la.grid, 1, 1, (unsigned)la.block, 1, 1, (unsigned)la.lds, la.stream, nullptr, cfg));
+            ctx->wave_spec_state = SF_WSPEC_SPECIALISED;
+            return SF_OK;
+        }
+        ctx->wave_spec_state = SF_WSPEC_FELL_BACK;
     }
     HIPCHK(ctx, pl.levels == 2 ? launch_tu_list_wave<2>(trace, pl.mode, la) : launch_tu_list_wave<4>(trace, pl.mode, la));
     return SF_OK;
@@ -2242,6 +2263,63 @@ extern "C" int32_t sf_debug_wave_plan(const int32_t* shape, int32_t n_shape, con
     if (msg) *msg = pl.msg;
     if (fits) fits[0] = wave_engine_fits(s), fits[1] = wave_engine_default(s);
     return pl.err;
+}
+
+// The run-time specialisation of the wave engine (sf_wave_spec.h; tests/test_wave_spec.py, tests/test_gpu_wave_spec.py).
+// sf_debug_wave_spec: out[0] state of the context's last wave launch (0 ahead-of-time, 1 specialised, 2 fell back), out[1] its reason code
+// (SF_WSPEC_R_*), out[2] compiles of the process, out[3] the last compile's milliseconds (rounded up), out[4..] the key (WaveSpecKey, 18 words).
+// `ctx` may be null: the process-wide figures alone.
+extern "C" int32_t sf_debug_wave_spec(const sf_ctx* ctx, int32_t* out, int32_t n_out) {
+    if (!out || n_out != 4 + (int)(sizeof(WaveSpecKey) / 4)) return SF_ERR_INVALID;
+    std::memset(out, 0, (size_t)n_out * 4);
+    if (ctx) out[0] = ctx->wave_spec_state, out[1] = ctx->wave_spec_reason, std::memcpy(out + 4, ctx->wave_spec_key, sizeof(WaveSpecKey));
+    WaveSpecCache& c = wave_spec_cache();
+    std::lock_guard<std::mutex> lock(c.mu);
+    out[2] = c.compiles, out[3] = (int32_t)std::ceil(c.last_ms);
+    return SF_OK;
+}
+// The LateAcceptance history of one replica as the search kernels keep it: out[n_slots][4] (n_slots = the configured history size) and the
+// cursor of the next step.  For parity tests of two kernels that must leave the same state behind.
+extern "C" int32_t sf_debug_late_acceptance(sf_ctx* ctx, int32_t replica, int64_t* out, int32_t n_slots, int32_t* cursor) {
+    if (!ctx || !out || !cursor || !ctx->search_alloc || replica < 0 || replica >= ctx->R || n_slots != ctx->sp.la_size) return SF_ERR_INVALID;
+    DeviceGuard guard(ctx);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpy(out, ctx->sp.la_hist + (size_t)replica * n_slots * 4, (size_t)n_slots * 32, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(cursor, ctx->sp.la_idx + replica, 4, hipMemcpyDeviceToHost));
+    return SF_OK;
+}
+// The policy on flat structs (WaveSpecGate): returns SF_WSPEC_R_NONE when the launch takes the specialised kernel, else the reason it does not.
+extern "C" int32_t sf_debug_wave_spec_gate(const int32_t* gate, int32_t n_gate) {
+    if (!gate || n_gate * 4 != (int)sizeof(WaveSpecGate)) return SF_ERR_INVALID;
+    WaveSpecGate g;
+    std::memcpy(&g, gate, sizeof g);
+    return wave_spec_wanted(g);
+}
+// One compile of the specialised unit for `arch` without a device: the option list (one option per line) into `opts`, the code object into the
+// file `out_path` (when given).  Returns the build's reason code (SF_WSPEC_R_NONE = compiled); `ms` receives the compile's milliseconds, `log`
+// the compiler's log.
+extern "C" int32_t sf_debug_wave_spec_compile(const int32_t* key, int32_t n_key, const char* arch, const char* out_path, char* opts, int32_t n_opts, char* log, int32_t n_log, double* ms) {
+    if (!key || n_key * 4 != (int)sizeof(WaveSpecKey) || !arch) return SF_ERR_INVALID;
+    WaveSpecKey k;
+    std::memcpy(&k, key, sizeof k);
+    if (!wave_spec_key_ok(k)) return SF_ERR_INVALID;
+    const std::string csrc = wave_spec_csrc();
+    auto put = [](char* dst, int32_t n, const std::string& s) {
+        if (dst && n > 0) std::snprintf(dst, (size_t)n, "%s", s.c_str());
+    };
+    std::string o;
+    for (auto& x : wave_spec_options(k, arch, csrc, wave_spec_rtc().include_dir)) o += x + "\n";
+    put(opts, n_opts, o);
+    if (!out_path) return SF_WSPEC_R_NONE;  // the options alone
+    const WaveSpecBuild b = wave_spec_compile(k, arch, csrc);
+    put(log, n_log, b.log);
+    if (ms) *ms = b.ms;
+    if (!b.reason) {
+        std::ofstream f(out_path, std::ios::binary);
+        f.write(b.code.data(), (std::streamsize)b.code.size());
+        if (!f) return SF_ERR_INVALID;
+    }
+    return b.reason;
 }
 
 // The order tables' 32-bit Barrett index (sf_common.h: perm_index_recip) on the host, for tests/test_wave_step_arith.py: no device, no context.

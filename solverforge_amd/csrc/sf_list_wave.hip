@@ -38,6 +38,48 @@ constexpr uint32_t NBR_END = 0xFFFFu;        // past the finite entries of the r
 #endif
 constexpr int WPB = SF_WPB;  // waves (= replicas) per workgroup
 
+// Constants of the model the kernel runs (fixed when sf_initialize returns).  Each goes through a macro that is the identity in the shipped
+// library; the device-only unit sf_tu_list_wave_spec.hip is compiled at run time with the macros defined as the context's literals
+// (`-DSF_SPEC_V(x)=100`), so everything derived from them -- the WCarve offsets, ring mask, reciprocals, field widths -- folds.
+#ifndef SF_SPEC_V
+#define SF_SPEC_V(x) (x)
+#endif
+#ifndef SF_SPEC_DIM
+#define SF_SPEC_DIM(x) (x)
+#endif
+#ifndef SF_SPEC_NCAP
+#define SF_SPEC_NCAP(x) (x)
+#endif
+#ifndef SF_SPEC_K0
+#define SF_SPEC_K0(x) (x)
+#endif
+#ifndef SF_SPEC_K1
+#define SF_SPEC_K1(x) (x)
+#endif
+// Candidates beyond those five, each behind its own switch and kept in the unit's default only where it measured faster than the unit without
+// it: the LateAcceptance history's size, the AcceptedCount limit, whether the internal node numbering exists (ListModel::perm /
+// inv), whether explicit step seeds exist -- and SF_SPEC_MODEL_WORDS (level_words below): capacity, weights, depot and the level words.
+#ifndef SF_SPEC_LA_SIZE
+#define SF_SPEC_LA_SIZE(x) (x)
+#endif
+#ifndef SF_SPEC_LIMIT
+#define SF_SPEC_LIMIT(x) (x)
+#endif
+#ifndef SF_SPEC_HAS_PERM
+#define SF_SPEC_HAS_PERM(x) (x)
+#endif
+#ifndef SF_SPEC_HAS_EXPLICIT
+#define SF_SPEC_HAS_EXPLICIT(x) (x)
+#endif
+// The run-time unit only (it defines SF_SPEC_L): the write-back forms its lane index again, behind an empty asm.  With V and n_cap literals the
+// replica's per-lane addresses of the prologue's state load and of the write-back become the same expressions, and the compiler carried them
+// across the whole step loop in scratch memory (16 B, 3 vector registers; the shipped kernels have none): DESIGN 21's finding, at another block.
+#ifdef SF_SPEC_L
+#define SF_SPEC_OWN_LANE(v) asm volatile("" : "+v"(v))
+#else
+#define SF_SPEC_OWN_LANE(v)
+#endif
+
 
 // wavefront-scope ordering of LDS/global traffic between lanes of one wave (no instruction cost:
 // a wave executes in lockstep and its DS/VMEM queues are in order; this pins the compiler).
@@ -331,7 +373,7 @@ __device__ __forceinline__ void apply_list_move_wave(const ListModel& m, uint16_
             }
         }
         if (a != b) {
-            for (uint32_t rr = lane; rr <= (uint32_t)m.V; rr += 64) {
+            for (uint32_t rr = lane; rr <= (uint32_t)SF_SPEC_V(m.V); rr += 64) {
                 if (a < b && rr > a && rr <= b) off[rr] -= 1;
                 if (a > b && rr > b && rr <= a) off[rr] += 1;
             }
@@ -356,7 +398,7 @@ __device__ __forceinline__ void apply_list_move_wave(const ListModel& m, uint16_
         relocate_flat_segment(visits, PY, zy, PX, lane, 64u, [] { wave_sync(); });            // Y X mid
         relocate_flat_segment(visits, PX + zy, zx, PY + zy, lane, 64u, [] { wave_sync(); });  // Y mid X
         if (a != b) {
-            for (uint32_t rr = lane; rr <= (uint32_t)m.V; rr += 64)
+            for (uint32_t rr = lane; rr <= (uint32_t)SF_SPEC_V(m.V); rr += 64)
                 if (rr > ox && rr <= oy) off[rr] = off[rr] + zy - zx;
             if (lane == 0 && m.demand) {
                 load[a] = (LT)wadd(wsub(load[a], da), db);
@@ -372,7 +414,7 @@ __device__ __forceinline__ void apply_list_move_wave(const ListModel& m, uint16_
         wave_sync();
         relocate_flat_segment(visits, P, z, Q, lane, 64u, [] { wave_sync(); });
         if (a != b) {
-            for (uint32_t rr = lane; rr <= (uint32_t)m.V; rr += 64) {
+            for (uint32_t rr = lane; rr <= (uint32_t)SF_SPEC_V(m.V); rr += 64) {
                 if (a < b && rr > a && rr <= b) off[rr] -= z;
                 if (a > b && rr > b && rr <= a) off[rr] += z;
             }
@@ -635,7 +677,7 @@ __device__ __forceinline__ bool eval_list_move_small(const ListModel& m, const u
     //   P2 (x,vq)   | (pb,x) | (x,nb)      M2 (pb,vq)*| (pb,y) | (y,nb)
     //   P3   -      | (x,nb) |   -         M3   -     | (y,nb) |   -          (* absent for a single-element source /
     //                                                                            an empty destination route)
-    const uint32_t dim4 = (uint32_t)m.dim * (M16 ? 2u : 4u);
+    const uint32_t dim4 = (uint32_t)SF_SPEC_DIM(m.dim) * (M16 ? 2u : 4u);
     auto leg = [&](uint32_t f, uint32_t t) -> uint32_t {
         const uint32_t byte_off = f * dim4 + t * (M16 ? 2u : 4u);  // dim <= 16384: < 2^30
         if (M16) return *(const uint16_t*)((const char*)m.mat16 + byte_off);  // every leg finite (MODE 2) and < 65535
@@ -698,6 +740,13 @@ __device__ __forceinline__ LevelWords<L> level_words(const ListModel& m) {
     LevelWords<L> w;
     w.cap = w.cw = w.dw = 0;
     w.depot = 0;
+#ifdef SF_SPEC_MODEL_WORDS  // the run-time unit, candidate "model words" (DESIGN 22): the literals themselves, nothing pinned in a register
+    w.cap = SF_SPEC_CAPACITY, w.cw = SF_SPEC_CAP_WEIGHT, w.dw = SF_SPEC_DIST_WEIGHT, w.depot = SF_SPEC_DEPOT;
+#pragma unroll
+    for (int k = 0; k < L; ++k) w.wc[k] = k == SF_SPEC_CAP_LEVEL ? 0xFFFFFFFFu : 0u, w.wd[k] = k == SF_SPEC_DIST_LEVEL ? 0xFFFFFFFFu : 0u;
+    w.has_cap = SF_SPEC_CAP_LEVEL >= 0 ? 1u : 0u;
+    return w;
+#endif
     if constexpr (KW) {
         // (through a vector register and back: pinned in place, a field stays a part of the register group its scalar load filled, and the group
         // is what gets spilled and read back)
@@ -744,7 +793,7 @@ __device__ __forceinline__ void eval_generated_small(const ListModel& m, const L
     const bool intra = a == b;
     const bool adj = !chg && intra && j == i + 1;
     const bool ca = chg || adj;
-    const uint32_t dim4 = (uint32_t)m.dim * (M16 ? 2u : 4u);
+    const uint32_t dim4 = (uint32_t)SF_SPEC_DIM(m.dim) * (M16 ? 2u : 4u);
     auto leg = [&](uint32_t f, uint32_t t) -> uint32_t {
         const uint32_t byte_off = __umul24(f, dim4) + t * (M16 ? 2u : 4u);  // node ids and the row pitch are below 2^24: one full-rate v_mad_u32_u24 (a 32-bit v_mul_lo is quarter rate); dim <= 16384: < 2^30
         if (M16) return *(const uint16_t*)((const char*)m.mat16 + byte_off);
@@ -864,12 +913,12 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
     const int rr = (int)(blockIdx.x * (blockDim.x >> 6) + wave_in_group);  // 1..WPB replicas per workgroup
     if (rr >= p.n_launch) return;  // no workgroup barrier anywhere below
     const int r = rr + p.replica_base;
-    const int V = m.V;
-    const uint32_t dim = (uint32_t)m.dim;
+    const int V = SF_SPEC_V(m.V);
+    const uint32_t dim = (uint32_t)SF_SPEC_DIM(m.dim);
 
     // leaf constants (no dynamic indexing of the kernarg block)
     const int n_leaves = FAST ? 2 : p.n_leaves;
-    const uint32_t K0 = (uint32_t)p.leaf[0].max_nearby, K1 = n_leaves > 1 ? (uint32_t)p.leaf[1].max_nearby : 1u;
+    const uint32_t K0 = (uint32_t)SF_SPEC_K0(p.leaf[0].max_nearby), K1 = n_leaves > 1 ? (uint32_t)SF_SPEC_K1(p.leaf[1].max_nearby) : 1u;
     const bool chg0 = FAST ? true : p.leaf[0].kind == 16, chg1 = FAST ? false : (n_leaves > 1 && p.leaf[1].kind == 16);
     const int acceptor = FAST ? 1 : p.acceptor, forager = FAST ? 0 : p.forager;
     const bool dry_run = FAST ? false : p.dry_run != 0;
@@ -885,7 +934,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
     auto desc0 = [&]() -> uint64_t { return SMALL ? (uint64_t)(int64_t)desc0_w : desc0_q; };
     auto desc1 = [&]() -> uint64_t { return SMALL ? (uint64_t)(int64_t)desc1_w : desc1_q; };
 
-    const WCarve cv(V, m.n_cap, m.dim, (int)(K0 > K1 ? K0 : K1), COMPACT, NODEG);
+    const WCarve cv(V, SF_SPEC_NCAP(m.n_cap), (int)dim, (int)(K0 > K1 ? K0 : K1), COMPACT, NODEG);
     const uint32_t RCM = cv.rc - 1;
     unsigned char* mem = smem + (size_t)wave_in_group * cv.total;
     LT* s_load = (LT*)(mem + cv.load);
@@ -916,7 +965,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
 
     // (SMALL uses the replica's base pointers for the load below only and forms them again at the write-back, from the argument block:
     // nothing of them is carried through the step loop)
-    uint32_t* g_visits = m.visits + (size_t)r * m.n_cap;
+    uint32_t* g_visits = m.visits + (size_t)r * SF_SPEC_NCAP(m.n_cap);
     uint32_t* g_off = m.off + (size_t)r * (V + 1);
     int64_t* g_load = m.load + (size_t)r * V;
     int64_t* g_score = m.score + (size_t)r * 4;
@@ -928,7 +977,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
     for (uint32_t t = lane; t < dim; t += 64) node_slot.clear(t);
     node_sync();
     const uint32_t total0 = uni(s_off[V]);
-    if (COMPACT && m.perm) {  // internal node numbering (ListModel::perm): the lists are renamed on the way in and on every way out
+    if (COMPACT && SF_SPEC_HAS_PERM(m.perm != nullptr)) {  // internal node numbering (ListModel::perm): the lists are renamed on the way in and on every way out
         for (uint32_t t = lane; t < total0; t += 64) s_visits[t] = m.perm[g_visits[t]];
     } else {
         for (uint32_t t = lane; t < total0; t += 64) s_visits[t] = (uint16_t)g_visits[t];
@@ -950,7 +999,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
             nsat += (uint32_t)__popcll(__ballot(lg));
         }
     }
-    auto ext_id = [&](uint32_t x) -> uint32_t { return (COMPACT && m.inv) ? (uint32_t)m.inv[x] : x; };  // an LDS element under the caller's numbering
+    auto ext_id = [&](uint32_t x) -> uint32_t { return (COMPACT && SF_SPEC_HAS_PERM(m.inv != nullptr)) ? (uint32_t)m.inv[x] : x; };  // an LDS element under the caller's numbering
     int64_t cur[L], best_sol[L];
 #pragma unroll
     for (int k = 0; k < L; ++k) {
@@ -1018,7 +1067,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
             const uint64_t draw = seed_draws0 + (uint64_t)step;
             const uint64_t* const explicit_seeds = SF_COLD_P(explicit_seeds);
             const int64_t n_explicit = SF_COLD_P(n_explicit);
-            if (explicit_seeds && (int64_t)draw < n_explicit)
+            if (SF_SPEC_HAS_EXPLICIT(explicit_seeds != nullptr) && (int64_t)draw < n_explicit)
                 sseed = explicit_seeds[(size_t)r * n_explicit + draw];
             else
                 sseed = step_seed(SF_COLD_P(random_seed) + (uint64_t)r, draw);
@@ -1031,7 +1080,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
         for (int k = 0; k < L; ++k) late.v[k] = 0;
         const int la_slot = la_cursor;  // LateAcceptance history slot of this step
         if (acceptor == 1 || acceptor == 4) {
-            const int64_t* const lh = SF_COLD_P(la_hist) + ((size_t)r * SF_COLD_P(la_size) + la_slot) * 4;
+            const int64_t* const lh = SF_COLD_P(la_hist) + ((size_t)r * SF_SPEC_LA_SIZE(SF_COLD_P(la_size)) + la_slot) * 4;
 #pragma unroll
             for (int k = 0; k < L; ++k) late.v[k] = (int64_t)uni64((uint64_t)lh[k]);
         }
@@ -1647,8 +1696,8 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                     // limit-th accepted lane, so the cut fires in it, `accepted` becomes `limit` and the step ends; a batch with fewer leaves
                     // `accepted` below the limit.  Cut and quit coincide: the step's end is decided here, not a second time at the batch's end.
                     consumed = valid;
-                    if (!RBATCH || (uint32_t)__popcll(accmask) >= (uint32_t)p.limit - accepted) {
-                        const uint32_t remaining = (uint32_t)p.limit - accepted;
+                    if (!RBATCH || (uint32_t)__popcll(accmask) >= (uint32_t)SF_SPEC_LIMIT(p.limit) - accepted) {
+                        const uint32_t remaining = (uint32_t)SF_SPEC_LIMIT(p.limit) - accepted;
                         const uint32_t pre = mbcnt64(accmask) + (acc ? 1u : 0u);
                         const uint64_t cutmask = __ballot(acc && pre == remaining);
                         nconsumed = cutmask ? (uint32_t)__ffsll((unsigned long long)cutmask) : nvalid;
@@ -1742,7 +1791,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
     #pragma unroll
                         for (int kk = 0; kk < L; ++kk) forager_thr.v[kk] = best_sol[kk];
                     }
-                    nconsumed = forager_chunk_cut<L>(forager, (uint32_t)p.limit, accepted, acc, sc, forager_thr, nvalid, improving_pick);
+                    nconsumed = forager_chunk_cut<L>(forager, (uint32_t)SF_SPEC_LIMIT(p.limit), accepted, acc, sc, forager_thr, nvalid, improving_pick);
                     consumed = lane < nconsumed;
                     if constexpr (!FAST)
                         if (annealing) sa_commit<L>(saw, p.sa, sach, nconsumed, lane);
@@ -1833,7 +1882,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                 C0.head += nconsumed - c1;
                 pulls += nconsumed;
                 if constexpr (!RBATCH)  // (RBATCH: decided at the cut)
-                    if (forager_quits(forager, (uint32_t)p.limit, accepted, has_best, improving_pick)) done = 1;
+                    if (forager_quits(forager, (uint32_t)SF_SPEC_LIMIT(p.limit), accepted, has_best, improving_pick)) done = 1;
             }
             ISA_MARK("replay_end");
             PH(3)
@@ -1860,7 +1909,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                 for (int kk = 0; kk < L; ++kk) bs.v[kk] = best_sol[kk];
                 if (!(score_cmp<L>(best, bs) > 0)) {  // leaving the best state: write its snapshot first
                     const uint32_t tot = uni(s_off[V]);
-                    uint32_t* const bv = SF_COLD_M(best_visits) + (size_t)r * SF_COLD_M(n_cap);
+                    uint32_t* const bv = SF_COLD_M(best_visits) + (size_t)r * SF_SPEC_NCAP(SF_COLD_M(n_cap));
                     uint32_t* const bo = SF_COLD_M(best_off) + (size_t)r * (V + 1);
                     // RANKTAB: the lane index is formed again HERE.  Taken from the kernel's `lane`, this cold block's per-lane LDS and global
                     // addresses are computed in the kernel's prologue and carried to it -- the kernel has no free vector register, so with the
@@ -1929,7 +1978,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                 for (int kk = 0; kk < L; ++kk) best_sol[kk] = cur[kk];
             }
             // acceptor.step_ended(last_step_score) always (step.rs:216-221)
-            const int la_size = SF_COLD_P(la_size);
+            const int la_size = SF_SPEC_LA_SIZE(SF_COLD_P(la_size));
             if ((acceptor == 1 || acceptor == 4) && lane == 0) {
                 int64_t* const lh = SF_COLD_P(la_hist) + ((size_t)r * la_size + la_slot) * 4;
 #pragma unroll
@@ -1975,8 +2024,10 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
         if constexpr (!FAST)
             if (annealing) sa_store(saw, p.sa, r, lane);
         const uint32_t tot = uni(s_off[V]);
+        uint32_t wlane = lane;
+        SF_SPEC_OWN_LANE(wlane);
         // SMALL: the replica's base pointers, formed again from the argument block
-        const size_t n_cap = (size_t)SF_COLD_M(n_cap);
+        const size_t n_cap = (size_t)SF_SPEC_NCAP(SF_COLD_M(n_cap));
         uint32_t* const w_visits = SMALL ? SF_COLD_M(visits) + (size_t)r * n_cap : g_visits;
         uint32_t* const w_off = SMALL ? SF_COLD_M(off) + (size_t)r * (V + 1) : g_off;
         int64_t* const w_load = SMALL ? SF_COLD_M(load) + (size_t)r * V : g_load;
@@ -1984,12 +2035,12 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
         if (best_pending) {  // the launch ends in a best state: its deferred snapshot
             uint32_t* const bv = SF_COLD_M(best_visits) + (size_t)r * n_cap;
             uint32_t* const bo = SF_COLD_M(best_off) + (size_t)r * (V + 1);
-            for (uint32_t t = lane; t < tot; t += 64) bv[t] = ext_id(s_visits[t]);
-            for (uint32_t t = lane; t <= (uint32_t)V; t += 64) bo[t] = s_off[t];
+            for (uint32_t t = wlane; t < tot; t += 64) bv[t] = ext_id(s_visits[t]);
+            for (uint32_t t = wlane; t <= (uint32_t)V; t += 64) bo[t] = s_off[t];
         }
-        for (uint32_t t = lane; t < tot; t += 64) w_visits[t] = ext_id(s_visits[t]);
-        for (uint32_t t = lane; t <= (uint32_t)V; t += 64) w_off[t] = s_off[t];
-        for (uint32_t t = lane; t < (uint32_t)V; t += 64) w_load[t] = (int64_t)s_load[t];
+        for (uint32_t t = wlane; t < tot; t += 64) w_visits[t] = ext_id(s_visits[t]);
+        for (uint32_t t = wlane; t <= (uint32_t)V; t += 64) w_off[t] = s_off[t];
+        for (uint32_t t = wlane; t < (uint32_t)V; t += 64) w_load[t] = (int64_t)s_load[t];
         if (lane == 0) {
 #pragma unroll
             for (int kk = 0; kk < L; ++kk) {
