@@ -1,6 +1,7 @@
 // Forager decisions of one 64-candidate replay chunk (lanes = pulls in union cursor order), shared by the four search
-// engines.  Restates phase/localsearch/forager.rs:157-420 (AcceptedCount / FirstAccepted / BestScore) and
-// forager/improving.rs:17-227 (FirstBestScoreImproving / FirstLastStepScoreImproving) for a whole chunk at once.
+// engines: where the step's pulls end (who the pick is afterwards: forager_pick_update in sf_step.h).  Restates
+// phase/localsearch/forager.rs:157-420 (AcceptedCount / FirstAccepted / BestScore) and forager/improving.rs:17-227
+// (FirstBestScoreImproving / FirstLastStepScoreImproving) for a whole chunk at once.
 #pragma once
 #include "sf_common.h"
 

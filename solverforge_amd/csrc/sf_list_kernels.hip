@@ -10,7 +10,7 @@
 //   runtime/compiler/executor/list_leaf/cursor/slot.rs:468-499 entity order w/o replacement
 //   heuristic/selector/decorator/vec_union.rs:334-362          StratifiedRandom union (2 leaves)
 //   phase/localsearch/phase/step.rs:30-225, phase/candidates.rs:47-285, evaluation.rs:20-115
-//   phase/localsearch/forager.rs:70-250, acceptor/{hill_climbing,late_acceptance}.rs
+//   phase/localsearch/forager.rs:70-250, acceptor/{hill_climbing,late_acceptance}.rs: the step protocol, one definition in sf_step.h
 //   heuristic/move/list_kernel/{change,swap}.rs               move semantics
 //   crates/solverforge-cvrp/src/{problem_data,meters}.rs      distance_cost / MatrixDistanceMeter
 //
@@ -30,25 +30,10 @@ namespace sf {
 // wave64 helpers
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
-__device__ __forceinline__ uint64_t lanemask_le(uint32_t lane) {
-    return lane == 63 ? ~0ULL : ((1ULL << (lane + 1)) - 1ULL);
-}
-__device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int src) {
-    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-    lo = __shfl(lo, src);
-    hi = __shfl(hi, src);
-    return ((uint64_t)hi << 32) | lo;
-}
 __device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v, int delta) {
     uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
     lo = __shfl_up(lo, delta);
     hi = __shfl_up(hi, delta);
-    return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
-    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-    lo = __shfl_xor(lo, m);
-    hi = __shfl_xor(hi, m);
     return ((uint64_t)hi << 32) | lo;
 }
 // wave64 inclusive prefix sum on the DPP network (row shifts + row broadcasts): no LDS crossbar
@@ -1368,23 +1353,6 @@ struct Carve {
     }
 };
 
-template <int L>
-__device__ __forceinline__ ScoreV<L> wave_max_score(ScoreV<L> s, bool valid) {
-    // lexicographic max across the wave; invalid lanes contribute -inf
-    if (!valid) {
-#pragma unroll
-        for (int k = 0; k < L; ++k) s.v[k] = INT64_MIN;
-    }
-#pragma unroll
-    for (int mlane = 32; mlane >= 1; mlane >>= 1) {
-        ScoreV<L> o;
-#pragma unroll
-        for (int k = 0; k < L; ++k) o.v[k] = (int64_t)shfl_xor_u64((uint64_t)s.v[k], mlane);
-        if (score_cmp<L>(o, s) > 0) s = o;
-    }
-    return s;
-}
-
 // Sorted top-K list held one entry per lane (lane i = i-th smallest key).
 struct TopK {
     uint64_t key;
@@ -1490,10 +1458,12 @@ __global__ __launch_bounds__(1024) void k_list_search(ListModel m, SearchParams 
             c.step_index = sidx;
             c.step_seed = sseed;
             StreamCtx ctx{sidx, sseed, p.order};
-            if (p.acceptor == 1) {
-                int idx = p.dry_run ? 0 : (int)((p.la_idx[r] + step) % p.la_size);
+            if (p.acceptor == 1) {  // (this engine carries no third threshold: the host refuses DiversifiedLateAcceptance for it)
+                const int idx = p.dry_run ? 0 : (int)((p.la_idx[r] + step) % p.la_size);
+                ScoreV<L> late, dla_thr;
+                step_begin<L>(1, p.la_hist + ((size_t)r * p.la_size + idx) * 4, p.dla_best + (size_t)r * 4, p.dla_tolerance, late, dla_thr);
 #pragma unroll
-                for (int k = 0; k < L; ++k) c.late[k] = p.la_hist[((size_t)r * p.la_size + idx) * 4 + k];
+                for (int k = 0; k < L; ++k) c.late[k] = late.v[k];
             }
             c.has_best = 0;
             c.equal_count = 0;
@@ -1754,13 +1724,8 @@ __global__ __launch_bounds__(1024) void k_list_search(ListModel m, SearchParams 
                         for (int kk = 0; kk < L; ++kk) sc.v[kk] = qs[kk];
                     }
                     const bool doable = valid && !(m0 & 0x80000000u);
-                    bool acc = false;
-                    if (doable) {
-                        if (p.acceptor == 0)
-                            acc = score_cmp<L>(sc, cur) > 0;
-                        else if (p.acceptor == 1)
-                            acc = score_cmp<L>(sc, cur) >= 0 || score_cmp<L>(sc, late) >= 0;
-                    }
+                    // acceptor 4 has no threshold here and accepts nothing (-1 is no acceptor of the test), should the host's refusal ever go
+                    bool acc = acceptor_accepts<L>(p.acceptor == 4 ? -1 : p.acceptor, doable, sc, cur, late, late);
                     SaChunk sach;
                     if (annealing) acc = sa_decide<L>(s_sa, p.sa, doable, sc, cur, lane, sach);
                     uint64_t accmask = __ballot(acc);
@@ -1771,53 +1736,13 @@ __global__ __launch_bounds__(1024) void k_list_search(ListModel m, SearchParams 
                     if (annealing) sa_commit<L>(s_sa, p.sa, sach, nconsumed, lane);
                     acc = acc && consumed;
                     accmask = __ballot(acc);
-                    if (accmask) {
-                        if (improving_pick) {  // BestCandidate::replace by the candidate that ends the step
-                            const int sel = (int)nconsumed - 1;
-#pragma unroll
-                            for (int kk = 0; kk < L; ++kk) best.v[kk] = (int64_t)shfl_u64((uint64_t)sc.v[kk], sel);
-                            best_m0 = __shfl(m0, sel);
-                            best_m1 = __shfl(m1, sel);
-                            best_kind = (int)__shfl(lf, sel);
-                            if (TRACE && lane == 0) c.best_ti = c.trace_n + (uint64_t)sel;
-                            equal_count = 1;
-                            has_best = 1;
-                        } else if (p.forager == 1) {
-                            if (!has_best) {
-                                const int sel = __ffsll((unsigned long long)accmask) - 1;
-#pragma unroll
-                                for (int kk = 0; kk < L; ++kk) best.v[kk] = (int64_t)shfl_u64((uint64_t)sc.v[kk], sel);
-                                best_m0 = __shfl(m0, sel);
-                                best_m1 = __shfl(m1, sel);
-                                best_kind = (int)__shfl(lf, sel);
-                                if (TRACE && lane == 0) c.best_ti = c.trace_n + (uint64_t)sel;
-                                has_best = 1;
-                            }
-                        } else {
-                            const ScoreV<L> M = wave_max_score<L>(sc, acc);
-                            const int cm = has_best ? score_cmp<L>(M, best) : 1;
-                            if (cm >= 0) {
-                                const bool newmax = cm > 0;
-                                const uint64_t base = newmax ? 0 : equal_count;
-                                const bool in_eq = acc && score_cmp<L>(sc, M) == 0;
-                                const uint64_t eq = __ballot(in_eq);
-                                const uint32_t rank = (uint32_t)__popcll(eq & lanemask_le(lane));
-                                const uint64_t cntq = base + rank;
-                                const bool pick = in_eq && ((newmax && rank == 1) ||
-                                                            (p.random_ties && cntq > 1 && reservoir_pick(c.step_seed, cntq)));
-                                const uint64_t pm = __ballot(pick);
-                                if (pm) {
-                                    const int sel = 63 - __clzll((unsigned long long)pm);
-                                    best_m0 = __shfl(m0, sel);
-                                    best_m1 = __shfl(m1, sel);
-                                    best_kind = (int)__shfl(lf, sel);
-                                    if (TRACE && lane == 0) c.best_ti = c.trace_n + (uint64_t)sel;
-                                }
-                                best = M;
-                                equal_count = base + (uint64_t)__popcll(eq);
-                                has_best = 1;
-                            }
-                        }
+                    const int sel = forager_pick_update<L>(p.forager, p.random_ties != 0, c.step_seed, acc, accmask, nconsumed, improving_pick, sc, best,
+                                                           equal_count, has_best);
+                    if (sel >= 0) {
+                        best_m0 = __shfl(m0, sel);
+                        best_m1 = __shfl(m1, sel);
+                        best_kind = (int)__shfl(lf, sel);
+                        if (TRACE && lane == 0) c.best_ti = c.trace_n + (uint64_t)sel;
                     }
                     const uint32_t nacc = (uint32_t)__popcll(accmask);
                     accepted += nacc;
@@ -1919,16 +1844,7 @@ __global__ __launch_bounds__(1024) void k_list_search(ListModel m, SearchParams 
         }
         if (!p.dry_run) {
             // update_best_solution (scope_progress.rs:89-107): clone on strict improvement
-            bool improved = false;
-            if (applied) {
-                ScoreV<L> cs, bs;
-#pragma unroll
-                for (int kk = 0; kk < L; ++kk) {
-                    cs.v[kk] = c.cur[kk];
-                    bs.v[kk] = c.best_sol[kk];
-                }
-                improved = score_cmp<L>(cs, bs) > 0;
-            }
+            const bool improved = step_improved<L>(applied, c.cur, c.best_sol);
             __syncthreads();
             if (improved) {
                 const uint32_t total = s_off[V];
@@ -1944,11 +1860,9 @@ __global__ __launch_bounds__(1024) void k_list_search(ListModel m, SearchParams 
                 }
             }
             if (tid == 0) {
-                // acceptor.step_ended(last_step_score) always (step.rs:216-221)
                 if (p.acceptor == 1) {
                     const int idx = (int)((p.la_idx[r] + step) % p.la_size);
-#pragma unroll
-                    for (int kk = 0; kk < L; ++kk) p.la_hist[((size_t)r * p.la_size + idx) * 4 + kk] = c.cur[kk];
+                    acceptor_step_ended<L>(1, true, c.cur, p.la_hist + ((size_t)r * p.la_size + idx) * 4, p.dla_best + (size_t)r * 4);
                 }
                 c.st[0] += 1;
             }

@@ -5,6 +5,7 @@
 #include "sf_common.h"
 #include "sf_anneal.h"
 #include "sf_forager.h"
+#include "sf_step.h"
 
 namespace sf {
 

@@ -1,0 +1,177 @@
+// The local-search step around one 64-candidate replay chunk (lanes = pulls in union cursor order), defined once -- called by the
+// block engine.  TODO: the wave engine (sf_list_wave.hip, general replay), the generic engine (sf_mixed_wave.hip), the fused scalar
+// engine (k_scalar_search_wave) and the provider step (k_scalar_step_decide) still hold their own copies of every rule below; a fix
+// to the tie-break has to be made there too (DESIGN 23 says why they are not callers yet): the acceptors without state (is_accepted of hill_climbing.rs, late_acceptance.rs:89-125,
+// diversified_late_acceptance.rs:139-159), the forager's pick (forager.rs:143-420, forager/improving.rs:92-95,205-208), and what a
+// step does before and after its candidates (step.rs:53-74,216-221, diversified_late_acceptance.rs:161-170,
+// scope_progress.rs:89-107).  A chunk goes through
+//     acceptor_accepts (or sa_decide, sf_anneal.h) -> forager_chunk_cut (sf_forager.h) -> [sa_commit] -> acc &= lane < nconsumed
+//     -> forager_pick_update -> forager_quits
+// Nothing here owns memory: the callers keep their registers and LDS words and pass references or row pointers.  SimulatedAnnealing
+// (sa_decide / sa_commit / sa_step_ended) and the statistics counters stay with the kernels.
+#pragma once
+#include "sf_common.h"
+#include "sf_forager.h"
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+
+namespace sf {
+
+// ---- wave64 primitives -------------------------------------------------------------------------------------------------------
+// A value every lane holds alike, said to the compiler: it moves to scalar registers.  Changes no value.
+__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ uint64_t uni64(uint64_t v) {
+    return ((uint64_t)uni((uint32_t)(v >> 32)) << 32) | (uint64_t)uni((uint32_t)v);
+}
+__device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int src) {
+    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+    lo = __shfl(lo, src);
+    hi = __shfl(hi, src);
+    return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
+    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+    lo = __shfl_xor(lo, m);
+    hi = __shfl_xor(hi, m);
+    return ((uint64_t)hi << 32) | lo;
+}
+template <int L>
+__device__ __forceinline__ ScoreV<L> wave_max_score(ScoreV<L> s, bool valid) {
+    // lexicographic max across the wave; invalid lanes contribute -inf
+    if (!valid) {
+#pragma unroll
+        for (int k = 0; k < L; ++k) s.v[k] = INT64_MIN;
+    }
+#pragma unroll
+    for (int mlane = 32; mlane >= 1; mlane >>= 1) {
+        ScoreV<L> o;
+#pragma unroll
+        for (int k = 0; k < L; ++k) o.v[k] = (int64_t)shfl_xor_u64((uint64_t)s.v[k], mlane);
+        if (score_cmp<L>(o, s) > 0) s = o;
+    }
+    return s;
+}
+
+template <int L>
+__device__ __forceinline__ ScoreV<L> score_of(const int64_t* w) {
+    ScoreV<L> s;
+#pragma unroll
+    for (int k = 0; k < L; ++k) s.v[k] = w[k];
+    return s;
+}
+
+// ---- step begin ----------------------------------------------------------------------------------------------------------------
+// The thresholds of the step: `late` = the LateAcceptance history slot of this step (la_row, read by acceptors 1 and 4), `dla_thr` =
+// DiversifiedLateAcceptance's best step score of the phase (dla_row) minus its tolerance band; both `late` where the acceptor has none.
+template <int L>
+__device__ __forceinline__ void step_begin(int acceptor, const int64_t* la_row, const int64_t* dla_row, double dla_tolerance, ScoreV<L>& late,
+                                           ScoreV<L>& dla_thr) {
+#pragma unroll
+    for (int k = 0; k < L; ++k) late.v[k] = 0;
+    if (acceptor == 1 || acceptor == 4) {
+#pragma unroll
+        for (int k = 0; k < L; ++k) late.v[k] = (int64_t)uni64((uint64_t)la_row[k]);
+    }
+    dla_thr = late;
+    if (acceptor == 4) {
+        ScoreV<L> db;
+#pragma unroll
+        for (int k = 0; k < L; ++k) db.v[k] = (int64_t)uni64((uint64_t)dla_row[k]);
+        dla_thr = dla_threshold<L>(db, dla_tolerance);
+    }
+}
+
+// ---- acceptor --------------------------------------------------------------------------------------------------------------------
+// is_accepted of HillClimbing (0), LateAcceptance (1) and DiversifiedLateAcceptance (4) for a candidate that reaches the acceptor
+// (`consult`: doable, and not held back by a gate of evaluation.rs:75-113); `cur` = the last step score.
+template <int L>
+__device__ __forceinline__ bool acceptor_accepts(int acceptor, bool consult, const ScoreV<L>& sc, const ScoreV<L>& cur, const ScoreV<L>& late,
+                                                 const ScoreV<L>& dla_thr) {
+    bool acc = false;
+    if (consult) {
+        if (acceptor == 0)
+            acc = score_cmp<L>(sc, cur) > 0;
+        else if (acceptor == 1)
+            acc = score_cmp<L>(sc, cur) >= 0 || score_cmp<L>(sc, late) >= 0;
+        else if (acceptor == 4)
+            acc = score_cmp<L>(sc, cur) >= 0 || score_cmp<L>(sc, late) >= 0 || score_cmp<L>(sc, dla_thr) >= 0;
+    }
+    return acc;
+}
+
+// ---- forager: who is the pick after this chunk --------------------------------------------------------------------------------
+// `acc` = accepted and consumed (after forager_chunk_cut and the re-masking), `accmask` its ballot.  Returns the lane whose candidate
+// becomes the step's pick, or -1 where the pick stays; the caller shuffles its own move words from that lane (two words and a leaf,
+// three in the generic engine, an index in the provider step), so each keeps them in the registers it chose.  `best`, `equal_count`
+// (EQ: the caller's width; the reservoir hashes it as 64 bits) and `has_best` are the forager's running state of the step, wave-uniform.
+//   improving_pick   BestCandidate::replace by the candidate that ends the step: lane nconsumed - 1
+//   FirstAccepted    the first accepted lane, once
+//   otherwise        the lexicographic maximum of the accepted lanes; among equals (of this chunk and the ones before) the first stays
+//                    unless random_ties lets the reservoir move the pick to a later one (forager.rs:143-148,245-263)
+// The test in front of the maximum only skips work: without an accepted lane at or above `best` the maximum is below it.
+template <int L, typename EQ>
+__device__ __forceinline__ int forager_pick_update(int forager, bool random_ties, uint64_t sseed, bool acc, uint64_t accmask, uint32_t nconsumed,
+                                                   bool improving_pick, const ScoreV<L>& sc, ScoreV<L>& best, EQ& equal_count, int& has_best) {
+    int sel = -1;
+    if (!accmask) return sel;
+    if (improving_pick) {
+        sel = (int)nconsumed - 1;
+#pragma unroll
+        for (int k = 0; k < L; ++k) best.v[k] = (int64_t)uni64(shfl_u64((uint64_t)sc.v[k], sel));
+        equal_count = 1;
+        has_best = 1;
+    } else if (forager == FORAGER_FIRST_ACCEPTED) {
+        if (!has_best) {
+            sel = __ffsll((unsigned long long)accmask) - 1;
+#pragma unroll
+            for (int k = 0; k < L; ++k) best.v[k] = (int64_t)uni64(shfl_u64((uint64_t)sc.v[k], sel));
+            has_best = 1;
+        }
+    } else if (!has_best || __ballot(acc && score_cmp<L>(sc, best) >= 0)) {
+        const ScoreV<L> M = wave_max_score<L>(sc, acc);
+        const int cm = has_best ? score_cmp<L>(M, best) : 1;
+        if (cm >= 0) {
+            const bool newmax = cm > 0;
+            const EQ eq_base = newmax ? 0 : equal_count;
+            const bool in_eq = acc && score_cmp<L>(sc, M) == 0;
+            const uint64_t eq = __ballot(in_eq);
+            const uint32_t rank = forager_mbcnt64(eq) + 1u;  // this lane's place among the chunk's equals, from 1
+            const uint64_t cntq = (uint64_t)eq_base + rank;
+            const bool pick = in_eq && ((newmax && rank == 1) || (random_ties && cntq > 1 && reservoir_pick(sseed, cntq)));
+            const uint64_t pm = __ballot(pick);
+            if (pm) sel = 63 - __clzll((unsigned long long)pm);
+#pragma unroll
+            for (int k = 0; k < L; ++k) best.v[k] = (int64_t)uni64((uint64_t)M.v[k]);
+            equal_count = eq_base + (EQ)__popcll(eq);
+            has_best = 1;
+        }
+    }
+    return sel;
+}
+
+// ---- step end ------------------------------------------------------------------------------------------------------------------
+// update_best_solution's test (scope_progress.rs:89-107): the step applied a move and its score beats the best one strictly
+template <int L>
+__device__ __forceinline__ bool step_improved(bool applied, const int64_t* cur, const int64_t* best_sol) {
+    return applied && score_cmp<L>(score_of<L>(cur), score_of<L>(best_sol)) > 0;
+}
+
+// acceptor.step_ended(last_step_score), always (step.rs:216-221), by the one lane `writer`: the LateAcceptance history slot of the step
+// takes the score; DiversifiedLateAcceptance keeps the phase's best step score (diversified_late_acceptance.rs:161-170)
+template <int L>
+__device__ __forceinline__ void acceptor_step_ended(int acceptor, bool writer, const int64_t* cur, int64_t* la_row, int64_t* dla_row) {
+    if ((acceptor == 1 || acceptor == 4) && writer) {
+#pragma unroll
+        for (int k = 0; k < L; ++k) la_row[k] = cur[k];
+    }
+    if (acceptor == 4 && writer) {
+        if (score_cmp<L>(score_of<L>(cur), score_of<L>(dla_row)) > 0) {
+#pragma unroll
+            for (int k = 0; k < L; ++k) dla_row[k] = cur[k];
+        }
+    }
+}
+
+}  // namespace sf
+#endif  // __HIPCC__
