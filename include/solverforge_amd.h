@@ -297,11 +297,19 @@ typedef enum sf_acceptor_kind {
                                        * scalar-only models (default_local_search/policy.rs:56-61).  Parameters:
                                        * sf_solver_configure_annealing; without it the reference defaults apply
                                        * (auto-calibrated, decay 0.999985, rng seed = random_seed). */
-    SF_ACCEPT_DIVERSIFIED_LATE_ACCEPTANCE = 4 /* phase/localsearch/acceptor/diversified_late_acceptance.rs:40-176; the default
+    SF_ACCEPT_DIVERSIFIED_LATE_ACCEPTANCE = 4,/* phase/localsearch/acceptor/diversified_late_acceptance.rs:40-176; the default
                                        * of grouped scalar-only models (default_local_search/policy.rs:52-55): late acceptance
                                        * over sf_solver_config::late_acceptance_size steps, or within `tolerance` of the best step
                                        * score of the phase (sf_solver_configure_diversified, default 0.01).  Wave, scalar and
                                        * generic engines (the block engine reports SF_ERR_UNSUPPORTED). */
+    SF_ACCEPT_GREAT_DELUGE = 5,       /* phase/localsearch/acceptor/great_deluge.rs:89-129: a candidate that beats the last step
+                                       * score, or is at or above a water level that starts at the phase's initial score and rises by
+                                       * |initial score|.multiply(rain_speed) at the end of every step (sf_solver_configure_great_deluge,
+                                       * default 0.001: builder/acceptor.rs:242-245).  Every engine. */
+    SF_ACCEPT_STEP_COUNTING_HILL_CLIMBING = 6 /* phase/localsearch/acceptor/step_counting.rs:85-129: a candidate that beats the last
+                                       * step score, or any candidate while fewer than step_count_limit steps have ended since the
+                                       * step score last beat the acceptor's best (sf_solver_configure_step_counting, default 100:
+                                       * builder/acceptor.rs:215-219).  Every engine. */
 } sf_acceptor_kind;
 
 typedef enum sf_annealing_mode {
@@ -780,6 +788,44 @@ typedef struct sf_anneal_chunk {
 } sf_anneal_chunk;
 int32_t sf_debug_anneal_chunks(sf_ctx* ctx, const sf_annealing_config* cfg, int32_t levels, int32_t hard_levels, int32_t n_chunks,
                                const sf_anneal_chunk* chunks, uint64_t* out_accept, uint64_t* out_state);
+/* rain_speed of SF_ACCEPT_GREAT_DELUGE (GreatDelugeAcceptor::new, great_deluge.rs:74-80; takes effect at the next sf_phase_start).  Any
+ * finite value is data, negative ones included, as in the reference; a non-finite one is SF_ERR_INVALID.  The water level rises by
+ * |initial score|.multiply(rain_speed) per step: every level (|x| as f64 * rain_speed).round() as i64, computed once per replica at phase
+ * start on the device.  Where |i64::MIN| or water + increment leaves i64 the reference panics in debug builds and wraps in release
+ * builds; the device wraps. */
+int32_t sf_solver_configure_great_deluge(sf_ctx* ctx, double rain_speed);
+/* step_count_limit of SF_ACCEPT_STEP_COUNTING_HILL_CLIMBING (StepCountingHillClimbingAcceptor::new, step_counting.rs:70-76; takes effect
+ * at the next sf_phase_start).
+ * SimulatedAnnealing, GreatDeluge and StepCountingHillClimbing share one state row per replica, which sf_phase_start initialises for the
+ * acceptor configured at that moment (acceptor.phase_started): after sf_solver_configure changes the acceptor to or from one of these
+ * three, call sf_phase_start before the next launch -- a launch without it would read the other acceptor's words. */
+int32_t sf_solver_configure_step_counting(sf_ctx* ctx, uint64_t step_count_limit);
+/* acceptor state of one replica (after sf_phase_start).  SF_ACCEPT_GREAT_DELUGE: out_level = the water level, out_increment = what every
+ * step end adds to it, *out_since = 0.  SF_ACCEPT_STEP_COUNTING_HILL_CLIMBING: out_level = the acceptor's best step score (not the
+ * solver's best solution), out_increment = zeros, *out_since = steps since it improved.  Levels past score_levels are zero.  Any other
+ * acceptor: SF_ERR_INVALID. */
+int32_t sf_get_acceptor_state(sf_ctx* ctx, int32_t replica, int64_t out_level[SF_MAX_LEVELS], int64_t out_increment[SF_MAX_LEVELS],
+                              uint64_t* out_since);
+/* Diagnostic: acceptors 5 and 6 alone, with the functions the search engines call (csrc/sf_step.h: acceptor_phase_started, step_begin,
+ * acceptor_accepts, acceptor_step_ended), on a script of records in one 64-lane launch (tests/test_gpu_acceptor_script.py).  The context
+ * gives device and stream only (no model needed); acceptor (5 / 6), levels (1..SF_MAX_LEVELS) and param_bits (rain_speed as f64 bits /
+ * step_count_limit) are those of this call.  Per record: op = SF_ACCEPTOR_OP_PHASE_STARTED (cur = the initial score), _DECIDE (cur = the
+ * last step score, sc[lane] = the trial score of candidate `lane`, bit `lane` of doable = the candidate reaches the acceptor) or
+ * _STEP_ENDED (cur = the step score).  Levels past `levels` are ignored.  The first record must be a phase start.
+ * out_accept[i] = the accept decision of the 64 candidates of a decide record (0 for the other ops); out_state[i] = the state words
+ * after record i: 0..3 level, 4..7 increment, 8 since.  n_records <= SF_ACCEPTOR_DEBUG_MAX_RECORDS. */
+#define SF_ACCEPTOR_STATE_WORDS 9
+#define SF_ACCEPTOR_DEBUG_MAX_RECORDS 65536
+typedef enum sf_acceptor_op { SF_ACCEPTOR_OP_PHASE_STARTED = 0, SF_ACCEPTOR_OP_DECIDE = 1, SF_ACCEPTOR_OP_STEP_ENDED = 2 } sf_acceptor_op;
+typedef struct sf_acceptor_record {
+    int64_t cur[SF_MAX_LEVELS];
+    int64_t sc[64][SF_MAX_LEVELS];
+    uint64_t doable;
+    int32_t op;
+    int32_t reserved; /* 0 */
+} sf_acceptor_record;
+int32_t sf_debug_acceptor_script(sf_ctx* ctx, int32_t acceptor, int32_t levels, uint64_t param_bits, int32_t n_records,
+                                 const sf_acceptor_record* records, uint64_t* out_accept, uint64_t* out_state);
 int32_t sf_solver_set_engine(sf_ctx* ctx, int32_t engine); /* sf_engine_kind; SF_ERR_UNSUPPORTED if it cannot run this model */
 int32_t sf_solver_get_engine(sf_ctx* ctx, int32_t* out_engine); /* the engine launches resolve to (after sf_initialize) */
 /* How the wave engine laid out its last fused launch (diagnostics; tests assert the path they mean to cover was taken):
@@ -868,8 +914,9 @@ int32_t sf_portfolio_destroy(sf_ctx* ctx);
  * ranked by best score (descending, ties to the lower index); the n_replace last ones adopt the best solution of the n_elite first ones
  * (adopter i takes elite i % n_elite) as their working and best solution: per-route aggregates rebuilt, cached / last-step / best score =
  * the elite's best score, LateAcceptance history restarted at that score; counters, step index and step seeds keep running, so the copies
- * diverge.  An adopter whose best score already equals its elite's is left alone.  List-only models, HC / LA / DLA acceptors; call between
- * launches (after sf_phase_start).  After a migration a replica's trajectory is no longer the reference's single-chain trajectory.
+ * diverge.  An adopter whose best score already equals its elite's is left alone.  List-only models, HC / LA / DLA acceptors -- every
+ * acceptor not listed here is refused with SF_ERR_UNSUPPORTED (SimulatedAnnealing, GreatDeluge, StepCountingHillClimbing: their state is
+ * a schedule of the phase that an adopted solution has no place in); call between launches (after sf_phase_start).  After a migration a replica's trajectory is no longer the reference's single-chain trajectory.
  * out_adopted (may be NULL) = replicas that took a copy. */
 int32_t sf_portfolio_migrate_local(sf_ctx* ctx, int32_t n_elite, int32_t n_replace, int32_t* out_adopted);
 

@@ -21,6 +21,9 @@ MOVE_DTYPE = np.dtype(
 # sf_anneal_chunk / SF_ANNEAL_STATE_WORDS (sf_debug_anneal_chunks)
 ANNEAL_CHUNK_DTYPE = np.dtype([("cur", "<i8", (4,)), ("sc", "<i8", (64, 4)), ("doable", "<u8"), ("nconsumed", "<i4"), ("step_end", "<i4")])
 ANNEAL_STATE_WORDS = 32
+# sf_acceptor_record / SF_ACCEPTOR_STATE_WORDS (sf_debug_acceptor_script): op 0 phase_started / 1 decide / 2 step_ended
+ACCEPTOR_RECORD_DTYPE = np.dtype([("cur", "<i8", (4,)), ("sc", "<i8", (64, 4)), ("doable", "<u8"), ("op", "<i4"), ("reserved", "<i4")])
+ACCEPTOR_STATE_WORDS = 9
 
 
 class SolverConfigStruct(C.Structure):
@@ -81,6 +84,7 @@ SYMBOLS = [
     "sf_constraint_add", "sf_constraint_add_list_precedence", "sf_selector_add", "sf_selector_add_sublist", "sf_selector_add_kopt", "sf_selector_add_permute", "sf_selector_add_precedence", "sf_list_set_precedence_policy", "sf_selector_add_ruin", "sf_selector_add_nearby_scalar", "sf_step_evaluate_compound", "sf_step_decide", "sf_step_decide_gated", "sf_step_decide_cursor", "sf_apply_compound", "sf_construct_list_cheapest", "sf_construct_list_regret", "sf_construct_list_clarke_wright", "sf_construct_list_round_robin", "sf_construct_list_k_opt", "sf_construct_scalar", "sf_list_set_time_windows", "sf_list_routes_feasible", "sf_list_time_window_path", "sf_list_force_time_window_walk", "sf_union_configure", "sf_schema_set_value_lists", "sf_initialize", "sf_evaluate_all", "sf_evaluate_each", "sf_get_scores",
     "sf_step_evaluate", "sf_apply", "sf_step_generate", "sf_solver_configure", "sf_default_local_search_components", "sf_solver_configure_default", "sf_solver_configure_annealing", "sf_solver_configure_diversified",
     "sf_get_annealing_state", "sf_debug_anneal_chunks", "sf_solver_set_step_seeds",
+    "sf_solver_configure_great_deluge", "sf_solver_configure_step_counting", "sf_get_acceptor_state", "sf_debug_acceptor_script",
     "sf_solver_set_engine", "sf_solver_get_engine", "sf_list_wave_layout", "sf_list_arith_flags", "sf_constraint_add_pair_join", "sf_constraint_add_uni_program", "sf_provider_declare", "sf_phase_start", "sf_solve_steps", "sf_solve_moves", "sf_solve_step_traced", "sf_get_stats", "sf_get_stats_sum", "sf_get_best_scores",
     "sf_profile_solve", "sf_download_scalar", "sf_download_list", "sf_portfolio_unique_id",
     "sf_portfolio_init", "sf_portfolio_allgather_best", "sf_portfolio_broadcast_best", "sf_portfolio_destroy", "sf_portfolio_migrate_local",
@@ -157,6 +161,10 @@ def load():
     L.sf_solver_configure_diversified.argtypes = [vp, C.c_double]
     L.sf_get_annealing_state.argtypes = [vp, i32, vp, C.POINTER(i32)]
     L.sf_debug_anneal_chunks.argtypes = [vp, C.POINTER(AnnealingConfigStruct), i32, i32, i32, vp, vp, vp]
+    L.sf_solver_configure_great_deluge.argtypes = [vp, C.c_double]
+    L.sf_solver_configure_step_counting.argtypes = [vp, u64]
+    L.sf_get_acceptor_state.argtypes = [vp, i32, vp, vp, C.POINTER(u64)]
+    L.sf_debug_acceptor_script.argtypes = [vp, i32, i32, u64, i32, vp, vp, vp]
     L.sf_solver_set_engine.argtypes = [vp, i32]
     L.sf_solver_get_engine.argtypes = [vp, C.POINTER(i32)]
     L.sf_list_wave_layout.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]

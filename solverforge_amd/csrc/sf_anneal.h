@@ -47,7 +47,7 @@ struct SaParams {
     int32_t never_accept_hard;         // HardRegressionPolicy::NeverAcceptHardRegression (:18-21)
     int32_t hard_levels;               // levels labelled ScoreLevel::Hard
     int32_t levels;                    // Score::levels_count()
-    uint64_t* state;                   // [R][SA_WORDS]
+    uint64_t* state;                   // [R][SA_WORDS]; under acceptors 5 and 6 a row's first AX_WORDS words are theirs (sf_step.h)
 };
 
 #if defined(__HIPCC__)

@@ -149,6 +149,8 @@ struct sf_ctx {
     sf_annealing_config anneal{SF_ANNEAL_CALIBRATED, 0, 128, 0, {0, 0, 0, 0}, 0.999985, 1.0e-9, 0.80, 1.0, 0};
     bool anneal_seed_set = false;
     double dla_tolerance = 0.01;  // DiversifiedLateAcceptanceAcceptor::default (diversified_late_acceptance.rs:106-110)
+    double gd_rain_speed = 0.001;        // GreatDeluge: water_level_increase_ratio.unwrap_or(0.001) (builder/acceptor.rs:242-245)
+    uint64_t sc_step_count_limit = 100;  // StepCountingHillClimbing: step_count_limit.unwrap_or(100) (builder/acceptor.rs:215-219)
     uint64_t* d_explicit = nullptr;
     int64_t n_explicit = 0;
     // trace buffers
@@ -1494,7 +1496,8 @@ int32_t sf_solver_configure(sf_ctx* ctx, const sf_solver_config* cfg) {
     if (ctx->search_alloc && cfg->late_acceptance_size > ctx->sp.la_size)
         return fail(ctx, SF_ERR_INVALID, "late_acceptance_size cannot grow after the search state exists");
     if (cfg->acceptor != SF_ACCEPT_HILL_CLIMBING && cfg->acceptor != SF_ACCEPT_LATE_ACCEPTANCE &&
-        cfg->acceptor != SF_ACCEPT_SIMULATED_ANNEALING && cfg->acceptor != SF_ACCEPT_DIVERSIFIED_LATE_ACCEPTANCE)
+        cfg->acceptor != SF_ACCEPT_SIMULATED_ANNEALING && cfg->acceptor != SF_ACCEPT_DIVERSIFIED_LATE_ACCEPTANCE &&
+        cfg->acceptor != SF_ACCEPT_GREAT_DELUGE && cfg->acceptor != SF_ACCEPT_STEP_COUNTING_HILL_CLIMBING)
         return fail(ctx, SF_ERR_UNSUPPORTED, "acceptor kind");
     if (cfg->forager < SF_FORAGER_ACCEPTED_COUNT || cfg->forager > SF_FORAGER_FIRST_LAST_STEP_SCORE_IMPROVING)
         return fail(ctx, SF_ERR_UNSUPPORTED, "forager");
@@ -1572,6 +1575,22 @@ int32_t sf_solver_configure_diversified(sf_ctx* ctx, double tolerance) {
     return SF_OK;
 }
 
+// GreatDelugeAcceptor::new(rain_speed) (great_deluge.rs:74-80): the reference takes any f64; a non-finite one would make every increment
+// 0 (NaN) or saturate it, which no configuration means
+int32_t sf_solver_configure_great_deluge(sf_ctx* ctx, double rain_speed) {
+    if (!ctx) return SF_ERR_INVALID;
+    if (!std::isfinite(rain_speed)) return fail(ctx, SF_ERR_INVALID, "great deluge: rain_speed must be finite");
+    ctx->gd_rain_speed = rain_speed;
+    return SF_OK;
+}
+
+// StepCountingHillClimbingAcceptor::new(step_count_limit) (step_counting.rs:70-76)
+int32_t sf_solver_configure_step_counting(sf_ctx* ctx, uint64_t step_count_limit) {
+    if (!ctx) return SF_ERR_INVALID;
+    ctx->sc_step_count_limit = step_count_limit;
+    return SF_OK;
+}
+
 // assert_simulated_annealing_parameters (simulated_annealing.rs:305-336) for a score of `levels` levels: nullptr, or what is wrong
 static const char* anneal_config_error(const sf_annealing_config* cfg, int levels) {
     auto temperature_ok = [](double v) { return std::isfinite(v) && v >= 0.0; };
@@ -1641,6 +1660,18 @@ static int anneal_phase_start(sf_ctx* ctx) {
     const uint64_t seed = ctx->anneal_seed_set ? a.seed : ctx->cfg.random_seed;
     std::vector<uint64_t> st((size_t)ctx->R * SA_WORDS, 0);
     for (int r = 0; r < ctx->R; ++r) anneal_init_state(a, ctx->levels, seed + (uint64_t)r, st.data() + (size_t)r * SA_WORDS);
+    // GreatDeluge / StepCountingHillClimbing keep their state at the head of the same rows (sf_step.h): zeros and the acceptor's parameter;
+    // the phase-start kernels fill in the rest from the initial score (acceptor_phase_started)
+    const int acceptor = ctx->cfg.acceptor;
+    if (acceptor == SF_ACCEPT_GREAT_DELUGE || acceptor == SF_ACCEPT_STEP_COUNTING_HILL_CLIMBING)
+        for (int r = 0; r < ctx->R; ++r) {
+            uint64_t* w = st.data() + (size_t)r * SA_WORDS;
+            std::fill(w, w + SA_WORDS, (uint64_t)0);
+            if (acceptor == SF_ACCEPT_GREAT_DELUGE)
+                std::memcpy(&w[AX_PARAM], &ctx->gd_rain_speed, 8);
+            else
+                w[AX_PARAM] = ctx->sc_step_count_limit;
+        }
     HIPCHK(ctx, hipMemcpyAsync(p.sa.state, st.data(), st.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return SF_OK;
@@ -1655,6 +1686,20 @@ int32_t sf_get_annealing_state(sf_ctx* ctx, int32_t replica, double* out_tempera
     HIPCHK(ctx, hipMemcpy(w, ctx->sp.sa.state + (size_t)replica * SA_WORDS, sizeof(w), hipMemcpyDeviceToHost));
     for (int k = 0; k < ctx->levels; ++k) std::memcpy(&out_temperatures[k], &w[SA_TEMP + k], 8);
     *out_calibrating = (int32_t)w[SA_CALIBRATING];
+    return SF_OK;
+}
+
+int32_t sf_get_acceptor_state(sf_ctx* ctx, int32_t replica, int64_t* out_level, int64_t* out_increment, uint64_t* out_since) {
+    DeviceGuard _dev(ctx);
+    if (!ctx || !ctx->search_alloc || replica < 0 || replica >= ctx->R || !out_level || !out_increment || !out_since)
+        return fail(ctx, SF_ERR_INVALID, "bad sf_get_acceptor_state");
+    if (ctx->sp.acceptor != SF_ACCEPT_GREAT_DELUGE && ctx->sp.acceptor != SF_ACCEPT_STEP_COUNTING_HILL_CLIMBING)  // the acceptor of the phase
+        return fail(ctx, SF_ERR_INVALID, "sf_get_acceptor_state: GreatDeluge or StepCountingHillClimbing");
+    uint64_t w[AX_WORDS];
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpy(w, ctx->sp.sa.state + (size_t)replica * SA_WORDS, sizeof(w), hipMemcpyDeviceToHost));
+    for (int k = 0; k < SF_MAX_LEVELS; ++k) out_level[k] = (int64_t)w[AX_LEVEL + k], out_increment[k] = (int64_t)w[AX_INCR + k];
+    *out_since = w[AX_SINCE];
     return SF_OK;
 }
 
@@ -1724,6 +1769,7 @@ int32_t sf_phase_start(sf_ctx* ctx) {
     HIPCHK(ctx, hipMemsetAsync(ctx->sp.seed_draws, 0, (size_t)ctx->R * 8, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->sp.stats, 0, (size_t)ctx->R * SF_STATS_WORDS * 8, ctx->stream));
     if ((rc = anneal_phase_start(ctx))) return rc;
+    ctx->sp.acceptor = ctx->cfg.acceptor;  // the phase-start kernels run acceptor.phase_started of GreatDeluge / StepCountingHillClimbing
     if ((rc = ruin_phase_start(ctx))) return rc;
     if (ctx->has_list_model)
         hipLaunchKernelGGL(k_list_phase_start, dim3(ctx->R), dim3(256), 0, ctx->stream, ctx->lm, ctx->sp);
@@ -1966,6 +2012,9 @@ static int launch_mixed(sf_ctx* ctx, SearchParams& p, int grid, bool trace) {
 extern "C" {
 
 static int launch_search(sf_ctx* ctx, SearchParams& p, int grid, bool trace) {
+    // GreatDeluge / StepCountingHillClimbing run in the TRACE instantiations of every engine (sf_step.h; with trace_replica = -1 nothing is
+    // traced): the untraced kernels, which every other policy runs, hold none of their code
+    trace = trace || p.acceptor == SF_ACCEPT_GREAT_DELUGE || p.acceptor == SF_ACCEPT_STEP_COUNTING_HILL_CLIMBING;
     // the 2-leaf nearby union has its own engines; every other union runs in the generic N-leaf engine
     // a configured root union (order / weights other than the default policy's) runs in the generic engine too
     bool nearby_scalar = false;  // the nearby scalar leaves live in the generic engine
@@ -2154,15 +2203,16 @@ int32_t sf_get_best_scores(sf_ctx* ctx, int64_t* out) {
 
 // Elite migration between the replicas of one context (extension; see k_list_migrate).  Replicas are ranked by their best score
 // (descending, ties to the lower index); the n_replace last ones adopt the best solution of the n_elite first ones, adopter i
-// taking elite i % n_elite.
+// taking elite i % n_elite.  Every acceptor the test below does not list is refused (SF_ERR_UNSUPPORTED).
 int32_t sf_portfolio_migrate_local(sf_ctx* ctx, int32_t n_elite, int32_t n_replace, int32_t* out_adopted) {
     DeviceGuard _dev(ctx);
     if (!ctx || !ctx->initialized) return fail(ctx, SF_ERR_INVALID, "sf_initialize first");
     if (!ctx->search_alloc) return fail(ctx, SF_ERR_INVALID, "sf_phase_start first");
     if (!ctx->has_list_model || ctx->has_scalar_model)
         return fail(ctx, SF_ERR_UNSUPPORTED, "elite migration: list-only models (the adopted state is the list class's best solution)");
-    if (ctx->cfg.acceptor == SF_ACCEPT_SIMULATED_ANNEALING)
-        return fail(ctx, SF_ERR_UNSUPPORTED, "elite migration: HillClimbing / LateAcceptance / DiversifiedLateAcceptance (an annealing replica keeps a temperature schedule)");
+    if (ctx->cfg.acceptor != SF_ACCEPT_HILL_CLIMBING && ctx->cfg.acceptor != SF_ACCEPT_LATE_ACCEPTANCE &&
+        ctx->cfg.acceptor != SF_ACCEPT_DIVERSIFIED_LATE_ACCEPTANCE)  // every acceptor not listed is refused: an adopted solution has no place in its schedule
+        return fail(ctx, SF_ERR_UNSUPPORTED, "elite migration: HillClimbing / LateAcceptance / DiversifiedLateAcceptance (an annealing replica keeps a temperature schedule, a great deluge its water level, a step count its best step score)");
     if (n_elite < 1 || n_replace < 0 || (int64_t)n_elite + n_replace > ctx->R)
         return fail(ctx, SF_ERR_INVALID, "elite migration: n_elite >= 1, n_replace >= 0, n_elite + n_replace <= replicas");
     if (out_adopted) *out_adopted = 0;
@@ -2356,3 +2406,4 @@ extern "C" int32_t sf_debug_phases(uint64_t* out8) {  // diagnostic builds only 
 #include "sf_portfolio.inc"
 #include "sf_candidate_trace.inc"
 #include "sf_api_anneal_debug.inc"
+#include "sf_api_acceptor_debug.inc"

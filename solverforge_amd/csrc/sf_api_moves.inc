@@ -216,8 +216,8 @@ static int32_t step_decide_impl(sf_ctx* ctx, int32_t replica, const sf_move_t* e
         return fail(ctx, SF_ERR_INVALID, "bad sf_step_decide arguments");
     if (!ctx->has_scalar_model || ctx->has_list_model) return fail(ctx, SF_ERR_UNSUPPORTED, "sf_step_decide: scalar-only models (ScalarCandidate edits)");
     if (int rc = compound_model_gates(ctx)) return rc;
-    if (ctx->cfg.acceptor != SF_ACCEPT_HILL_CLIMBING && ctx->cfg.acceptor != SF_ACCEPT_LATE_ACCEPTANCE && ctx->cfg.acceptor != SF_ACCEPT_DIVERSIFIED_LATE_ACCEPTANCE)
-        return fail(ctx, SF_ERR_UNSUPPORTED, "sf_step_decide: HillClimbing, LateAcceptance or DiversifiedLateAcceptance");
+    if (ctx->cfg.acceptor == SF_ACCEPT_SIMULATED_ANNEALING)
+        return fail(ctx, SF_ERR_UNSUPPORTED, "sf_step_decide: HillClimbing, LateAcceptance, DiversifiedLateAcceptance, GreatDeluge or StepCountingHillClimbing");
     if (offsets[0] != 0) return fail(ctx, SF_ERR_INVALID, "offsets[0] must be 0");
     if (n >= ((int64_t)1 << 31)) return fail(ctx, SF_ERR_UNSUPPORTED, "sf_step_decide: fewer than 2^31 candidates");
     for (int64_t i = 0; i < n; ++i)

@@ -1254,6 +1254,7 @@ __global__ __launch_bounds__(256) void k_list_phase_start(ListModel m, SearchPar
         p.la_idx[r] = 0;
         p.step_index[r] = 0;
         p.has_best[r] = 1;
+        acceptor_phase_started(p.acceptor, cur, p.sa.state + (size_t)r * SA_WORDS);  // GreatDeluge / StepCountingHillClimbing
     }
 }
 
@@ -1675,6 +1676,11 @@ __global__ __launch_bounds__(1024) void k_list_search(ListModel m, SearchParams 
                     late.v[kk] = c.late[kk];
                     forager_best.v[kk] = c.best_sol[kk];
                 }
+                // GreatDeluge / StepCountingHillClimbing (the TRACE instantiations carry them): this wave reads their threshold of the step
+                // itself; the state row is written at step end only, behind the workgroup barriers
+                [[maybe_unused]] bool thr_on = true;
+                if constexpr (TRACE)
+                    if (p.acceptor == 5 || p.acceptor == 6) ax_step_begin<L>(p.acceptor, p.sa.state + (size_t)r * SA_WORDS, late, thr_on);
                 uint32_t best_m0 = c.best_m0, best_m1 = c.best_m1;
                 int best_kind = c.best_kind;
                 uint64_t st_gen = 0, st_acc = 0, st_calc = 0, st_nd = 0;
@@ -1726,6 +1732,8 @@ __global__ __launch_bounds__(1024) void k_list_search(ListModel m, SearchParams 
                     const bool doable = valid && !(m0 & 0x80000000u);
                     // acceptor 4 has no threshold here and accepts nothing (-1 is no acceptor of the test), should the host's refusal ever go
                     bool acc = acceptor_accepts<L>(p.acceptor == 4 ? -1 : p.acceptor, doable, sc, cur, late, late);
+                    if constexpr (TRACE)
+                        if (p.acceptor == 5 || p.acceptor == 6) acc = ax_accepts<L>(doable, sc, cur, late, thr_on);
                     SaChunk sach;
                     if (annealing) acc = sa_decide<L>(s_sa, p.sa, doable, sc, cur, lane, sach);
                     uint64_t accmask = __ballot(acc);
@@ -1864,6 +1872,8 @@ __global__ __launch_bounds__(1024) void k_list_search(ListModel m, SearchParams 
                     const int idx = (int)((p.la_idx[r] + step) % p.la_size);
                     acceptor_step_ended<L>(1, true, c.cur, p.la_hist + ((size_t)r * p.la_size + idx) * 4, p.dla_best + (size_t)r * 4);
                 }
+                if constexpr (TRACE)
+                    if (p.acceptor == 5 || p.acceptor == 6) ax_step_ended<L>(p.acceptor, true, c.cur, p.sa.state + (size_t)r * SA_WORDS);
                 c.st[0] += 1;
             }
             if (annealing && wave == 0) sa_step_ended(s_sa, p.sa, lane);

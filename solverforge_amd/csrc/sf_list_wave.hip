@@ -1087,6 +1087,9 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
             for (int k = 0; k < L; ++k) db.v[k] = (int64_t)uni64((uint64_t)p.dla_best[(size_t)r * 4 + k]);
             dla_thr = dla_threshold<L>(db, p.dla_tolerance);
         }
+        [[maybe_unused]] bool thr_on = true;  // GreatDeluge / StepCountingHillClimbing (the TRACE instantiations carry them): their threshold of the step in `late` (sf_step.h)
+        if constexpr (TRACE)
+            if (acceptor == 5 || acceptor == 6) ax_step_begin<L>(acceptor, p.sa.state + (size_t)r * SA_WORDS, late, thr_on);
         int has_best = 0;
         typename std::conditional<SMALL, uint32_t, uint64_t>::type equal_count = 0;  // (SMALL: 32 bits -- a step consumes far fewer than 2^32 candidates; reservoir_pick hashes it as 64 bits)
         uint32_t accepted = 0, pulls = 0;
@@ -1778,6 +1781,8 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                         else if (acceptor == 4)
                             acc = score_cmp<L>(sc, curv) >= 0 || score_cmp<L>(sc, late) >= 0 || score_cmp<L>(sc, dla_thr) >= 0;
                     }
+                    if constexpr (TRACE)
+                        if (acceptor == 5 || acceptor == 6) acc = ax_accepts<L>(doable, sc, curv, late, thr_on);
                     SaChunk sach;
                     if constexpr (!FAST)
                         if (annealing) acc = sa_decide<L>(saw, p.sa, doable, sc, curv, lane, sach);
@@ -1992,6 +1997,8 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                     for (int kk = 0; kk < L; ++kk) p.dla_best[(size_t)r * 4 + kk] = cur[kk];
                 }
             }
+            if constexpr (TRACE)
+                if (acceptor == 5 || acceptor == 6) ax_step_ended<L>(acceptor, lane == 0, cur, p.sa.state + (size_t)r * SA_WORDS);
             if constexpr (!FAST)
                 if (annealing) sa_step_ended(saw, p.sa, lane);
             wave_sync();

@@ -1055,6 +1055,9 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
             for (int k = 0; k < L; ++k) db.v[k] = (int64_t)uni64((uint64_t)p.dla_best[(size_t)r * 4 + k]);
             dla_thr = dla_threshold<L>(db, p.dla_tolerance);
         }
+        [[maybe_unused]] bool thr_on = true;  // GreatDeluge / StepCountingHillClimbing (the TRACE instantiations carry them): their threshold of the step in `late` (sf_step.h)
+        if constexpr (TRACE)
+            if (acceptor == 5 || acceptor == 6) ax_step_begin<L>(acceptor, p.sa.state + (size_t)r * SA_WORDS, late, thr_on);
         int has_best = 0;
         uint64_t equal_count = 0;
         uint32_t accepted = 0;
@@ -2538,6 +2541,8 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                     else if (acceptor == 4)
                         acc = score_cmp<L>(sc, curv) >= 0 || score_cmp<L>(sc, late) >= 0 || score_cmp<L>(sc, dla_thr) >= 0;
                 }
+                if constexpr (TRACE)
+                    if (acceptor == 5 || acceptor == 6) acc = ax_accepts<L>(consult, sc, curv, late, thr_on);
                 SaChunk sach;
                 if (annealing) acc = sa_decide<L>(saw, p.sa, consult, sc, curv, lane, sach);
                 uint64_t accmask = __ballot(acc);
@@ -2858,6 +2863,8 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                     for (int kk = 0; kk < L; ++kk) p.dla_best[(size_t)r * 4 + kk] = cur[kk];
                 }
             }
+            if constexpr (TRACE)
+                if (acceptor == 5 || acceptor == 6) ax_step_ended<L>(acceptor, lane == 0, cur, p.sa.state + (size_t)r * SA_WORDS);
             if (annealing) sa_step_ended(saw, p.sa, lane);
             wave_sync();
             st_steps += 1;

@@ -954,7 +954,7 @@ __global__ __launch_bounds__(64) void k_scalar_apply_compound(ScalarModel m, int
 
 // One HOST-DRIVEN local-search step (sf_step_decide): the candidates were generated on the host (a ScalarCandidateProvider behind a
 // GroupedScalarMoveSelector, builder/selector/grouped_scalar.rs) and scored by k_scalar_evaluate_compound; this wave pulls them in
-// order through the configured acceptor (HillClimbing / LateAcceptance / DiversifiedLateAcceptance) and forager exactly like the
+// order through the configured acceptor (HillClimbing / LateAcceptance / DiversifiedLateAcceptance / GreatDeluge / StepCountingHillClimbing) and forager exactly like the
 // fused engines (phase/candidates.rs:47-285), commits the pick (CompoundScalarMove::do_move) and ends the step (step.rs:122-221):
 // acceptor.step_ended, best solution, counters, step index.  One wavefront, replica `replica`.
 SF_PLAIN_KERNEL
@@ -997,6 +997,8 @@ __global__ __launch_bounds__(64) void k_scalar_step_decide(ScalarModel m, Search
         for (int k = 0; k < L; ++k) db.v[k] = p.dla_best[(size_t)r * 4 + k];
         dla_thr = dla_threshold<L>(db, p.dla_tolerance);
     }
+    bool thr_on = true;  // GreatDeluge / StepCountingHillClimbing: their threshold of the step in `late` (sf_step.h)
+    if (p.acceptor == 5 || p.acceptor == 6) ax_step_begin<L>(p.acceptor, p.sa.state + (size_t)r * SA_WORDS, late, thr_on);
     const uint64_t draw = p.seed_draws[r];
     const uint64_t sseed = (p.explicit_seeds && (int64_t)draw < p.n_explicit) ? p.explicit_seeds[(size_t)r * p.n_explicit + draw]
                                                                             : step_seed(p.random_seed + (uint64_t)r, draw);
@@ -1046,6 +1048,7 @@ __global__ __launch_bounds__(64) void k_scalar_step_decide(ScalarModel m, Search
             else if (p.acceptor == 4)
                 acc = score_cmp<L>(sc, curv) >= 0 || score_cmp<L>(sc, late) >= 0 || score_cmp<L>(sc, dla_thr) >= 0;
         }
+        if (p.acceptor == 5 || p.acceptor == 6) acc = ax_accepts<L>(consult, sc, curv, late, thr_on);
         bool improving_pick = false;
         const ScoreV<L> forager_thr = p.forager == FORAGER_FIRST_BEST_IMPROVING ? best_sol : curv;
         const uint32_t nconsumed = forager_chunk_cut<L>(p.forager, (uint32_t)p.limit, accepted, acc, sc, forager_thr, nvalid, improving_pick);
@@ -1132,6 +1135,7 @@ __global__ __launch_bounds__(64) void k_scalar_step_decide(ScalarModel m, Search
                 for (int k = 0; k < L; ++k) p.dla_best[(size_t)r * 4 + k] = curv.v[k];
             }
         }
+        if (p.acceptor == 5 || p.acceptor == 6) ax_step_ended<L>(p.acceptor, true, curv.v, p.sa.state + (size_t)r * SA_WORDS);
         p.la_idx[r] = la_slot + 1 >= p.la_size ? 0 : la_slot + 1;
         p.step_index[r] += 1;
         p.seed_draws[r] += 1;
@@ -1413,6 +1417,7 @@ __global__ __launch_bounds__(256) void k_scalar_phase_start(ScalarModel m, Searc
         p.la_idx[r] = 0;
         p.step_index[r] = 0;
         p.has_best[r] = 1;
+        acceptor_phase_started(p.acceptor, cur, p.sa.state + (size_t)r * SA_WORDS);  // GreatDeluge / StepCountingHillClimbing
     }
 }
 
@@ -1580,6 +1585,9 @@ __global__ __launch_bounds__(64 * 4, SF_SCALAR_BLOCKS_PER_CU) void k_scalar_sear
             for (int k = 0; k < L; ++k) db.v[k] = (int64_t)uni64((uint64_t)p.dla_best[(size_t)r * 4 + k]);
             dla_thr = dla_threshold<L>(db, p.dla_tolerance);
         }
+        [[maybe_unused]] bool thr_on = true;  // GreatDeluge / StepCountingHillClimbing (the TRACE instantiations carry them): their threshold of the step in `late` (sf_step.h)
+        if constexpr (TRACE)
+            if (p.acceptor == 5 || p.acceptor == 6) ax_step_begin<L>(p.acceptor, p.sa.state + (size_t)r * SA_WORDS, late, thr_on);
         int has_best = 0;
         uint64_t equal_count = 0;
         uint32_t accepted = 0, pulls = 0;
@@ -1785,6 +1793,8 @@ __global__ __launch_bounds__(64 * 4, SF_SCALAR_BLOCKS_PER_CU) void k_scalar_sear
                     else if (p.acceptor == 4)
                         acc = score_cmp<L>(sc, curv) >= 0 || score_cmp<L>(sc, late) >= 0 || score_cmp<L>(sc, dla_thr) >= 0;
                 }
+                if constexpr (TRACE)
+                    if (p.acceptor == 5 || p.acceptor == 6) acc = ax_accepts<L>(doable, sc, curv, late, thr_on);
                 SaChunk sach;
                 if (annealing) acc = sa_decide<L>(saw, p.sa, doable, sc, curv, lane, sach);
                 uint64_t accmask = __ballot(acc);
@@ -1953,6 +1963,8 @@ __global__ __launch_bounds__(64 * 4, SF_SCALAR_BLOCKS_PER_CU) void k_scalar_sear
                     for (int kk = 0; kk < L; ++kk) p.dla_best[(size_t)r * 4 + kk] = cur[kk];
                 }
             }
+            if constexpr (TRACE)
+                if (p.acceptor == 5 || p.acceptor == 6) ax_step_ended<L>(p.acceptor, lane == 0, cur, p.sa.state + (size_t)r * SA_WORDS);
             if (annealing) sa_step_ended(saw, p.sa, lane);
             wave_sync();
             st_steps += 1;

@@ -1,17 +1,37 @@
-// The local-search step around one 64-candidate replay chunk (lanes = pulls in union cursor order), defined once -- called by the
-// block engine.  TODO: the wave engine (sf_list_wave.hip, general replay), the generic engine (sf_mixed_wave.hip), the fused scalar
-// engine (k_scalar_search_wave) and the provider step (k_scalar_step_decide) still hold their own copies of every rule below; a fix
-// to the tie-break has to be made there too (DESIGN 23 says why they are not callers yet): the acceptors without state (is_accepted of hill_climbing.rs, late_acceptance.rs:89-125,
-// diversified_late_acceptance.rs:139-159), the forager's pick (forager.rs:143-420, forager/improving.rs:92-95,205-208), and what a
-// step does before and after its candidates (step.rs:53-74,216-221, diversified_late_acceptance.rs:161-170,
-// scope_progress.rs:89-107).  A chunk goes through
-//     acceptor_accepts (or sa_decide, sf_anneal.h) -> forager_chunk_cut (sf_forager.h) -> [sa_commit] -> acc &= lane < nconsumed
-//     -> forager_pick_update -> forager_quits
+// The local-search step around one 64-candidate replay chunk (lanes = pulls in union cursor order).  Two groups of rules, with different callers:
+//
+// 1. The acceptors without state of their own (is_accepted of hill_climbing.rs, late_acceptance.rs:89-125,
+//    diversified_late_acceptance.rs:139-159), the forager's pick (forager.rs:143-420, forager/improving.rs:92-95,205-208), and what a step
+//    does before and after its candidates (step.rs:53-74,216-221, diversified_late_acceptance.rs:161-170, scope_progress.rs:89-107):
+//    step_begin, acceptor_accepts, forager_pick_update, step_improved, acceptor_step_ended.  Called by the block engine only.  The wave
+//    engine's general replay (sf_list_wave.hip), the generic engine (sf_mixed_wave.hip), the fused scalar engine (k_scalar_search_wave)
+//    and the provider step (k_scalar_step_decide) hold their own copies of these rules (DESIGN 23 says why): a fix to the tie-break has to
+//    be made there too.  A chunk goes through
+//        acceptor_accepts (or sa_decide, sf_anneal.h) -> forager_chunk_cut (sf_forager.h) -> [sa_commit] -> acc &= lane < nconsumed
+//        -> forager_pick_update -> forager_quits
+// 2. GreatDeluge (5, great_deluge.rs:89-129) and StepCountingHillClimbing (6, step_counting.rs:85-129): acceptor_phase_started,
+//    ax_step_begin, ax_accepts, ax_step_ended.  Defined here alone and called from all five places.  In the four fused engines the calls
+//    are compiled into the TRACE instantiations only, and a launch under these two acceptors takes those: the untraced
+//    kernels, which every other policy runs, hold none of this code.
+//
 // Nothing here owns memory: the callers keep their registers and LDS words and pass references or row pointers.  SimulatedAnnealing
 // (sa_decide / sa_commit / sa_step_ended) and the statistics counters stay with the kernels.
 #pragma once
+#include "sf_anneal.h"
 #include "sf_common.h"
 #include "sf_forager.h"
+
+namespace sf {
+// State of acceptors 5 and 6: AX_WORDS words per replica at the head of the replica's acceptor-state row (SaParams::state, [R][SA_WORDS]; one
+// acceptor runs at a time, and SimulatedAnnealing's words are rewritten at every phase start).  The search kernels' argument block keeps
+// its layout this way, so the kernels that never run these acceptors load every field from the offset they had.
+//   AX_LEVEL  4  GreatDeluge: the water level.  StepCounting: the best step score since the count was reset (the acceptor's own "best")
+//   AX_INCR   4  GreatDeluge: |initial score| x rain_speed per level, fixed at phase start.  StepCounting: zeros
+//   AX_SINCE  1  StepCounting: steps since that best score improved.  GreatDeluge: 0
+//   AX_PARAM  1  from the host at phase start: rain_speed (f64 bits) / step_count_limit
+enum : int { AX_LEVEL = 0, AX_INCR = 4, AX_SINCE = 8, AX_PARAM = 9, AX_WORDS = 10 };
+static_assert(AX_WORDS <= SA_WORDS, "acceptors 5 and 6 live in the replica's acceptor-state row");
+}  // namespace sf
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -82,6 +102,24 @@ __device__ __forceinline__ void step_begin(int acceptor, const int64_t* la_row, 
     }
 }
 
+// Acceptors 5 and 6 (ax_row, read wave-uniform) say their rule as one threshold and one flag, so a candidate costs two compares:
+//     accepted  <=>  sc > cur  ||  (thr_on && sc >= late)
+//   GreatDeluge     late = the water level, thr_on
+//   StepCounting    since < limit: every candidate passes, late = the least score, thr_on;  else thr_on is off: sc > cur alone
+template <int L>
+__device__ __forceinline__ void ax_step_begin(int acceptor, const uint64_t* ax_row, ScoreV<L>& late, bool& thr_on) {
+    thr_on = true;
+    if (acceptor == 5) {
+#pragma unroll
+        for (int k = 0; k < L; ++k) late.v[k] = (int64_t)uni64(ax_row[AX_LEVEL + k]);
+    }
+    if (acceptor == 6) {
+        thr_on = uni64(ax_row[AX_SINCE]) < uni64(ax_row[AX_PARAM]);
+#pragma unroll
+        for (int k = 0; k < L; ++k) late.v[k] = INT64_MIN;
+    }
+}
+
 // ---- acceptor --------------------------------------------------------------------------------------------------------------------
 // is_accepted of HillClimbing (0), LateAcceptance (1) and DiversifiedLateAcceptance (4) for a candidate that reaches the acceptor
 // (`consult`: doable, and not held back by a gate of evaluation.rs:75-113); `cur` = the last step score.
@@ -98,6 +136,12 @@ __device__ __forceinline__ bool acceptor_accepts(int acceptor, bool consult, con
             acc = score_cmp<L>(sc, cur) >= 0 || score_cmp<L>(sc, late) >= 0 || score_cmp<L>(sc, dla_thr) >= 0;
     }
     return acc;
+}
+// is_accepted of GreatDeluge (5) and StepCountingHillClimbing (6): the first compare is strict (great_deluge.rs:90-106,
+// step_counting.rs:86-99); `late` / `thr_on` from ax_step_begin
+template <int L>
+__device__ __forceinline__ bool ax_accepts(bool consult, const ScoreV<L>& sc, const ScoreV<L>& cur, const ScoreV<L>& late, bool thr_on) {
+    return consult && (score_cmp<L>(sc, cur) > 0 || (thr_on && score_cmp<L>(sc, late) >= 0));
 }
 
 // ---- forager: who is the pick after this chunk --------------------------------------------------------------------------------
@@ -157,6 +201,25 @@ __device__ __forceinline__ bool step_improved(bool applied, const int64_t* cur, 
     return applied && score_cmp<L>(score_of<L>(cur), score_of<L>(best_sol)) > 0;
 }
 
+// ---- phase start ---------------------------------------------------------------------------------------------------------------
+// acceptor.phase_started(initial_score) of acceptors 5 and 6, by one thread of the phase-start kernels; `initial` and the state rows are
+// four words wide whatever the score's width (levels it does not have are zero and stay zero).
+//   GreatDeluge (great_deluge.rs:108-111)    water = initial; the increment of every step_ended, initial.abs().multiply(rain_speed), is
+//       constant over the phase and kept: per level (|x| as f64 * rain_speed).round() as i64 (score/macros.rs:61-63, bendable.rs:142-152) --
+//       one f64 multiply, round half away from zero, the cast saturates and maps NaN to 0, as in dla_threshold.  |INT64_MIN| wraps.
+//   StepCounting (step_counting.rs:101-104)   best = initial, since = 0
+__device__ __forceinline__ void acceptor_phase_started(int acceptor, const int64_t* initial, uint64_t* ax_row) {
+    if (acceptor != 5 && acceptor != 6) return;
+    double rain_speed;
+    __builtin_memcpy(&rain_speed, &ax_row[AX_PARAM], 8);
+    for (int k = 0; k < 4; ++k) {
+        const int64_t a = initial[k] < 0 ? wsub(0, initial[k]) : initial[k];
+        ax_row[AX_LEVEL + k] = (uint64_t)initial[k];
+        ax_row[AX_INCR + k] = acceptor == 5 ? (uint64_t)f64_as_i64(__builtin_round((double)a * rain_speed)) : 0u;
+    }
+    ax_row[AX_SINCE] = 0;
+}
+
 // acceptor.step_ended(last_step_score), always (step.rs:216-221), by the one lane `writer`: the LateAcceptance history slot of the step
 // takes the score; DiversifiedLateAcceptance keeps the phase's best step score (diversified_late_acceptance.rs:161-170)
 template <int L>
@@ -169,6 +232,27 @@ __device__ __forceinline__ void acceptor_step_ended(int acceptor, bool writer, c
         if (score_cmp<L>(score_of<L>(cur), score_of<L>(dla_row)) > 0) {
 #pragma unroll
             for (int k = 0; k < L; ++k) dla_row[k] = cur[k];
+        }
+    }
+}
+// ... of acceptors 5 and 6: GreatDeluge's water rises by its increment (great_deluge.rs:113-123; the sum wraps); StepCounting resets its
+// count when the step score beats its best strictly and counts the step otherwise (step_counting.rs:106-123)
+template <int L>
+__device__ __forceinline__ void ax_step_ended(int acceptor, bool writer, const int64_t* cur, uint64_t* ax_row) {
+    if (acceptor == 5 && writer) {
+#pragma unroll
+        for (int k = 0; k < L; ++k) ax_row[AX_LEVEL + k] = (uint64_t)wadd((int64_t)ax_row[AX_LEVEL + k], (int64_t)ax_row[AX_INCR + k]);
+    }
+    if (acceptor == 6 && writer) {
+        ScoreV<L> b;
+#pragma unroll
+        for (int k = 0; k < L; ++k) b.v[k] = (int64_t)ax_row[AX_LEVEL + k];
+        if (score_cmp<L>(score_of<L>(cur), b) > 0) {
+#pragma unroll
+            for (int k = 0; k < L; ++k) ax_row[AX_LEVEL + k] = (uint64_t)cur[k];
+            ax_row[AX_SINCE] = 0;
+        } else {
+            ax_row[AX_SINCE] += 1;
         }
     }
 }

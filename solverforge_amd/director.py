@@ -12,7 +12,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import (ANNEAL_CHUNK_DTYPE, ANNEAL_STATE_WORDS, MOVE_DTYPE, AnnealingConfigStruct, ScalarConstructionConfigStruct, SolverConfigStruct, SolverForgeError, StatsStruct,
+from ._lib import (ACCEPTOR_RECORD_DTYPE, ACCEPTOR_STATE_WORDS, ANNEAL_CHUNK_DTYPE, ANNEAL_STATE_WORDS, MOVE_DTYPE, AnnealingConfigStruct, ScalarConstructionConfigStruct, SolverConfigStruct, SolverForgeError, StatsStruct,
                    check, ptr)
 
 
@@ -40,6 +40,8 @@ class Acceptor:
     HILL_CLIMBING, LATE_ACCEPTANCE = 0, 1
     SIMULATED_ANNEALING = 3  # default of scalar-only models (default_local_search/policy.rs:56-61)
     DIVERSIFIED_LATE_ACCEPTANCE = 4  # default of grouped scalar-only models (default_local_search/policy.rs:52-55)
+    GREAT_DELUGE = 5  # great_deluge.rs:89-129; configure_great_deluge
+    STEP_COUNTING_HILL_CLIMBING = 6  # step_counting.rs:85-129; configure_step_counting
 
 
 class AnnealingMode:
@@ -592,6 +594,37 @@ class GpuScoreDirector:
         """Tolerance of AcceptorKind.DIVERSIFIED_LATE_ACCEPTANCE (DiversifiedLateAcceptanceAcceptor::new); the history size
         is SolverConfig.late_acceptance_size."""
         check(self._L.sf_solver_configure_diversified(self._h, float(tolerance)), self._h)
+
+    def configure_great_deluge(self, rain_speed=0.001):
+        """rain_speed of Acceptor.GREAT_DELUGE (GreatDelugeAcceptor::new; default builder/acceptor.rs:242-245); takes effect at the
+        next phase_start.  Any finite value."""
+        check(self._L.sf_solver_configure_great_deluge(self._h, float(rain_speed)), self._h)
+
+    def configure_step_counting(self, step_count_limit=100):
+        """step_count_limit of Acceptor.STEP_COUNTING_HILL_CLIMBING (StepCountingHillClimbingAcceptor::new; default
+        builder/acceptor.rs:215-219), 0 .. 2^64 - 1; takes effect at the next phase_start."""
+        check(self._L.sf_solver_configure_step_counting(self._h, int(step_count_limit)), self._h)
+
+    def acceptor_state(self, replica=0):
+        """(level, increment, since) of one replica under GREAT_DELUGE (water level, its increment per step, 0) or
+        STEP_COUNTING_HILL_CLIMBING (the acceptor's best step score, zeros, steps since it improved); int64[levels] each."""
+        lv, inc = np.zeros(4, dtype=np.int64), np.zeros(4, dtype=np.int64)
+        since = C.c_uint64(0)
+        check(self._L.sf_get_acceptor_state(self._h, replica, ptr(lv), ptr(inc), C.byref(since)), self._h)
+        return lv[:self.levels].copy(), inc[:self.levels].copy(), int(since.value)
+
+    def debug_acceptor_script(self, acceptor, records, levels=2, rain_speed=0.001, step_count_limit=100):
+        """sf_debug_acceptor_script: the engines' GreatDeluge / StepCountingHillClimbing code alone on a scripted sequence.  records: array
+        of ACCEPTOR_RECORD_DTYPE (cur[4], sc[64][4], doable mask, op 0 phase_started / 1 decide / 2 step_ended), the first one a phase
+        start.  Returns (accept masks u64[n], state words u64[n, 9] after every record: level[4], increment[4], since).  The context's own
+        model and configuration play no part."""
+        records = np.ascontiguousarray(records, dtype=ACCEPTOR_RECORD_DTYPE)
+        n = len(records)
+        bits = int(np.float64(rain_speed).view(np.uint64)) if acceptor == Acceptor.GREAT_DELUGE else int(step_count_limit)
+        accept = np.zeros(max(n, 1), dtype=np.uint64)
+        state = np.zeros((max(n, 1), ACCEPTOR_STATE_WORDS), dtype=np.uint64)
+        check(self._L.sf_debug_acceptor_script(self._h, int(acceptor), levels, bits, n, ptr(records), ptr(accept), ptr(state)), self._h)
+        return accept[:n], state[:n]
 
     def annealing_state(self, replica=0):
         """(current temperatures per score level, still calibrating?) of one replica's acceptor."""
