@@ -306,10 +306,18 @@ typedef enum sf_acceptor_kind {
                                        * score, or is at or above a water level that starts at the phase's initial score and rises by
                                        * |initial score|.multiply(rain_speed) at the end of every step (sf_solver_configure_great_deluge,
                                        * default 0.001: builder/acceptor.rs:242-245).  Every engine. */
-    SF_ACCEPT_STEP_COUNTING_HILL_CLIMBING = 6 /* phase/localsearch/acceptor/step_counting.rs:85-129: a candidate that beats the last
+    SF_ACCEPT_STEP_COUNTING_HILL_CLIMBING = 6,/* phase/localsearch/acceptor/step_counting.rs:85-129: a candidate that beats the last
                                        * step score, or any candidate while fewer than step_count_limit steps have ended since the
                                        * step score last beat the acceptor's best (sf_solver_configure_step_counting, default 100:
                                        * builder/acceptor.rs:215-219).  Every engine. */
+    SF_ACCEPT_TABU_SEARCH = 7         /* phase/localsearch/acceptor/tabu_search.rs:64-237: a candidate whose move signature is in none of
+                                       * the entity / value / move / undo-move memories, or whose score beats the acceptor's best step
+                                       * score (aspiration).  Policy: sf_solver_configure_tabu, which has to be called BEFORE
+                                       * sf_solver_configure names this kind (NULL or all four sizes absent: move-only 10,
+                                       * builder/acceptor.rs:383-405); until then the kind is SF_ERR_UNSUPPORTED ("acceptor kind").  Scalar change / swap, nearby scalar, list change / swap and
+                                       * nearby list leaves, in the fused scalar, wave and generic engines (mixed models included);
+                                       * every other leaf, the block engine, sf_step_decide* and elite migration report
+                                       * SF_ERR_UNSUPPORTED. */
 } sf_acceptor_kind;
 
 typedef enum sf_annealing_mode {
@@ -826,6 +834,56 @@ typedef struct sf_acceptor_record {
 } sf_acceptor_record;
 int32_t sf_debug_acceptor_script(sf_ctx* ctx, int32_t acceptor, int32_t levels, uint64_t param_bits, int32_t n_records,
                                  const sf_acceptor_record* records, uint64_t* out_accept, uint64_t* out_state);
+/* Policy of SF_ACCEPT_TABU_SEARCH (TabuSearchPolicy, tabu_search.rs:12-55; normalize_tabu_search_policy, builder/acceptor.rs:383-405;
+ * takes effect at the next sf_phase_start).  A size below 0 means the dimension is absent; all four absent is move_only(10); an explicit
+ * 0 is SF_ERR_INVALID with the reference's message ("tabu_search field `entity_tabu_size` must be greater than 0").  move_tabu_size and
+ * undo_move_tabu_size above SF_TABU_MAX_TENURE_MOVE: SF_ERR_UNSUPPORTED.  cfg == NULL restores the default.
+ * TabuSearch keeps its fixed words in the state row that SimulatedAnnealing, GreatDeluge and StepCountingHillClimbing use and its memories
+ * in an arena that sf_phase_start sizes and clears: after sf_solver_configure changes the acceptor to or from a stateful kind, call
+ * sf_phase_start before the next launch.  A launch under TabuSearch in a phase that was not started under it is SF_ERR_INVALID. */
+#define SF_TABU_MAX_TENURE_MOVE 64
+typedef struct sf_tabu_config {
+    int64_t entity_tabu_size, value_tabu_size, move_tabu_size, undo_move_tabu_size; /* < 0: absent */
+    int32_t aspiration_enabled; /* default 1 */
+    int32_t reserved;           /* 0 */
+} sf_tabu_config;
+int32_t sf_solver_configure_tabu(sf_ctx* ctx, const sf_tabu_config* cfg);
+/* TabuSearch state of one replica (after sf_phase_start under SF_ACCEPT_TABU_SEARCH; any other acceptor: SF_ERR_INVALID).
+ * out_best = the acceptor's best step score (not the solver's best solution), levels past score_levels zero; out_pushes = pushes into
+ * the entity / value / move / undo memory since phase start.  Entity and value memories: the SET of tokens currently tabu, ascending
+ * (token = scope base + entity index / scope base + value index + 1, None = base + 0; the FIFO order of duplicates is not observable
+ * and not stored); at most cap_entity / cap_value are written, *out_n_entity / *out_n_value = how many there are.  Move and undo
+ * memories: the live identities, oldest to newest, two words each (csrc/sf_tabu.h: tabu_pack), out_moves / out_undo hold
+ * 2 * SF_TABU_MAX_TENURE_MOVE words. */
+int32_t sf_get_tabu_state(sf_ctx* ctx, int32_t replica, int64_t out_best[SF_MAX_LEVELS], uint64_t out_pushes[4], int64_t cap_entity,
+                          uint32_t* out_entity, int64_t* out_n_entity, int64_t cap_value, uint32_t* out_value, int64_t* out_n_value,
+                          uint64_t* out_moves, int32_t* out_n_moves, uint64_t* out_undo, int32_t* out_n_undo);
+/* Diagnostic: the TabuSearch code of the engines (csrc/sf_tabu.h: tabu_phase_started, tabu_step_begin, tabu_accepts, tabu_step_ended)
+ * alone on a script of records in one 64-lane launch (tests/test_gpu_tabu_script.py).  The context gives device and stream only.
+ * policy as in sf_solver_configure_tabu; levels 1..SF_MAX_LEVELS; n_entity_ids / n_value_ids = sizes of the two token tables (every
+ * token of every signature is below them or SF_TABU_NO_TOKEN).  Per record: op = SF_ACCEPTOR_OP_PHASE_STARTED (score = the initial score),
+ * _DECIDE (sc[lane], sig[lane] = trial score and signature of candidate `lane`, bit `lane` of reach = it reaches the acceptor) or
+ * _STEP_ENDED (score = the step score, has_sig != 0: sig[0] is the applied move's signature).  The first record must be a phase start.
+ * out_accept[i] = the ballot of a decide record (0 otherwise).  out_state[i] = the state after record i, a row of
+ * SF_TABU_STATE_FIXED + n_entity_ids + n_value_ids + 4 * SF_TABU_MAX_TENURE_MOVE words: best[4], pushes[4], tenures[4], aspiration,
+ * three reserved words; the entity stamps (1-based ordinal of the token's latest push, 0 = never; zeros without an entity tenure); the
+ * value stamps; the move ring and the undo ring in slot order (slot = push ordinal % tenure), two words per identity. */
+#define SF_TABU_NO_TOKEN 0xFFFFFFFFu
+#define SF_TABU_STATE_FIXED 16
+typedef struct sf_tabu_signature {
+    uint32_t entity[2], value[2];
+    uint64_t move_id[2], undo_move_id[2];
+} sf_tabu_signature;
+typedef struct sf_tabu_record {
+    int64_t score[SF_MAX_LEVELS];
+    int64_t sc[64][SF_MAX_LEVELS];
+    sf_tabu_signature sig[64];
+    uint64_t reach;
+    int32_t op;
+    int32_t has_sig;
+} sf_tabu_record;
+int32_t sf_debug_tabu_script(sf_ctx* ctx, const sf_tabu_config* policy, int32_t levels, int32_t n_entity_ids, int32_t n_value_ids,
+                             int32_t n_records, const sf_tabu_record* records, uint64_t* out_accept, uint64_t* out_state);
 int32_t sf_solver_set_engine(sf_ctx* ctx, int32_t engine); /* sf_engine_kind; SF_ERR_UNSUPPORTED if it cannot run this model */
 int32_t sf_solver_get_engine(sf_ctx* ctx, int32_t* out_engine); /* the engine launches resolve to (after sf_initialize) */
 /* How the wave engine laid out its last fused launch (diagnostics; tests assert the path they mean to cover was taken):
@@ -915,7 +973,7 @@ int32_t sf_portfolio_destroy(sf_ctx* ctx);
  * (adopter i takes elite i % n_elite) as their working and best solution: per-route aggregates rebuilt, cached / last-step / best score =
  * the elite's best score, LateAcceptance history restarted at that score; counters, step index and step seeds keep running, so the copies
  * diverge.  An adopter whose best score already equals its elite's is left alone.  List-only models, HC / LA / DLA acceptors -- every
- * acceptor not listed here is refused with SF_ERR_UNSUPPORTED (SimulatedAnnealing, GreatDeluge, StepCountingHillClimbing: their state is
+ * acceptor not listed here is refused with SF_ERR_UNSUPPORTED (SimulatedAnnealing, GreatDeluge, StepCountingHillClimbing, TabuSearch: their state is
  * a schedule of the phase that an adopted solution has no place in); call between launches (after sf_phase_start).  After a migration a replica's trajectory is no longer the reference's single-chain trajectory.
  * out_adopted (may be NULL) = replicas that took a copy. */
 int32_t sf_portfolio_migrate_local(sf_ctx* ctx, int32_t n_elite, int32_t n_replace, int32_t* out_adopted);

@@ -24,6 +24,18 @@ ANNEAL_STATE_WORDS = 32
 # sf_acceptor_record / SF_ACCEPTOR_STATE_WORDS (sf_debug_acceptor_script): op 0 phase_started / 1 decide / 2 step_ended
 ACCEPTOR_RECORD_DTYPE = np.dtype([("cur", "<i8", (4,)), ("sc", "<i8", (64, 4)), ("doable", "<u8"), ("op", "<i4"), ("reserved", "<i4")])
 ACCEPTOR_STATE_WORDS = 9
+# sf_tabu_signature / sf_tabu_record / SF_TABU_* (sf_debug_tabu_script, sf_get_tabu_state)
+TABU_SIGNATURE_DTYPE = np.dtype([("entity", "<u4", (2,)), ("value", "<u4", (2,)), ("move_id", "<u8", (2,)), ("undo_move_id", "<u8", (2,))])
+TABU_RECORD_DTYPE = np.dtype([("score", "<i8", (4,)), ("sc", "<i8", (64, 4)), ("sig", TABU_SIGNATURE_DTYPE, (64,)), ("reach", "<u8"), ("op", "<i4"), ("has_sig", "<i4")])
+TABU_STATE_FIXED = 16
+TABU_MAX_TENURE_MOVE = 64
+TABU_NO_TOKEN = 0xFFFFFFFF
+
+
+class TabuConfigStruct(C.Structure):
+    # sf_tabu_config: a size below 0 = the dimension is absent
+    _fields_ = [("entity_tabu_size", C.c_int64), ("value_tabu_size", C.c_int64), ("move_tabu_size", C.c_int64), ("undo_move_tabu_size", C.c_int64),
+                ("aspiration_enabled", C.c_int32), ("reserved", C.c_int32)]
 
 
 class SolverConfigStruct(C.Structure):
@@ -85,6 +97,7 @@ SYMBOLS = [
     "sf_step_evaluate", "sf_apply", "sf_step_generate", "sf_solver_configure", "sf_default_local_search_components", "sf_solver_configure_default", "sf_solver_configure_annealing", "sf_solver_configure_diversified",
     "sf_get_annealing_state", "sf_debug_anneal_chunks", "sf_solver_set_step_seeds",
     "sf_solver_configure_great_deluge", "sf_solver_configure_step_counting", "sf_get_acceptor_state", "sf_debug_acceptor_script",
+    "sf_solver_configure_tabu", "sf_get_tabu_state", "sf_debug_tabu_script",
     "sf_solver_set_engine", "sf_solver_get_engine", "sf_list_wave_layout", "sf_list_arith_flags", "sf_constraint_add_pair_join", "sf_constraint_add_uni_program", "sf_provider_declare", "sf_phase_start", "sf_solve_steps", "sf_solve_moves", "sf_solve_step_traced", "sf_get_stats", "sf_get_stats_sum", "sf_get_best_scores",
     "sf_profile_solve", "sf_download_scalar", "sf_download_list", "sf_portfolio_unique_id",
     "sf_portfolio_init", "sf_portfolio_allgather_best", "sf_portfolio_broadcast_best", "sf_portfolio_destroy", "sf_portfolio_migrate_local",
@@ -165,6 +178,9 @@ def load():
     L.sf_solver_configure_step_counting.argtypes = [vp, u64]
     L.sf_get_acceptor_state.argtypes = [vp, i32, vp, vp, C.POINTER(u64)]
     L.sf_debug_acceptor_script.argtypes = [vp, i32, i32, u64, i32, vp, vp, vp]
+    L.sf_solver_configure_tabu.argtypes = [vp, C.POINTER(TabuConfigStruct)]
+    L.sf_get_tabu_state.argtypes = [vp, i32, vp, vp, i64, vp, C.POINTER(i64), i64, vp, C.POINTER(i64), vp, C.POINTER(i32), vp, C.POINTER(i32)]
+    L.sf_debug_tabu_script.argtypes = [vp, C.POINTER(TabuConfigStruct), i32, i32, i32, i32, vp, vp, vp]
     L.sf_solver_set_engine.argtypes = [vp, i32]
     L.sf_solver_get_engine.argtypes = [vp, C.POINTER(i32)]
     L.sf_list_wave_layout.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]

@@ -151,6 +151,11 @@ struct sf_ctx {
     double dla_tolerance = 0.01;  // DiversifiedLateAcceptanceAcceptor::default (diversified_late_acceptance.rs:106-110)
     double gd_rain_speed = 0.001;        // GreatDeluge: water_level_increase_ratio.unwrap_or(0.001) (builder/acceptor.rs:242-245)
     uint64_t sc_step_count_limit = 100;  // StepCountingHillClimbing: step_count_limit.unwrap_or(100) (builder/acceptor.rs:215-219)
+    uint64_t tabu_tenure[4] = {0, 0, 10, 0};  // TabuSearch: entity / value / move / undo tenures, 0 = absent; default move_only(10) (builder/acceptor.rs:383-405)
+    int tabu_aspire = 1;
+    bool tabu_configured = false;  // sf_solver_configure_tabu was called: acceptor kind 7 is taken only then (sf_solver_configure)
+    uint64_t* d_tabu_arena = nullptr;  // [R][arena words of the policy and the model] stamp tables and rings (sf_tabu.h), sized at sf_phase_start
+    uint64_t tabu_arena_cap = 0;
     uint64_t* d_explicit = nullptr;
     int64_t n_explicit = 0;
     // trace buffers
@@ -1497,8 +1502,11 @@ int32_t sf_solver_configure(sf_ctx* ctx, const sf_solver_config* cfg) {
         return fail(ctx, SF_ERR_INVALID, "late_acceptance_size cannot grow after the search state exists");
     if (cfg->acceptor != SF_ACCEPT_HILL_CLIMBING && cfg->acceptor != SF_ACCEPT_LATE_ACCEPTANCE &&
         cfg->acceptor != SF_ACCEPT_SIMULATED_ANNEALING && cfg->acceptor != SF_ACCEPT_DIVERSIFIED_LATE_ACCEPTANCE &&
-        cfg->acceptor != SF_ACCEPT_GREAT_DELUGE && cfg->acceptor != SF_ACCEPT_STEP_COUNTING_HILL_CLIMBING)
+        cfg->acceptor != SF_ACCEPT_GREAT_DELUGE && cfg->acceptor != SF_ACCEPT_STEP_COUNTING_HILL_CLIMBING && cfg->acceptor != SF_ACCEPT_TABU_SEARCH)
         return fail(ctx, SF_ERR_UNSUPPORTED, "acceptor kind");
+    // TabuSearch is the one acceptor whose policy is a call of its own: the kind is taken once that call was made (NULL = the default policy)
+    if (cfg->acceptor == SF_ACCEPT_TABU_SEARCH && !ctx->tabu_configured)
+        return fail(ctx, SF_ERR_UNSUPPORTED, "acceptor kind 7 (TabuSearch): call sf_solver_configure_tabu first (NULL for the default policy, move-only 10)");
     if (cfg->forager < SF_FORAGER_ACCEPTED_COUNT || cfg->forager > SF_FORAGER_FIRST_LAST_STEP_SCORE_IMPROVING)
         return fail(ctx, SF_ERR_UNSUPPORTED, "forager");
     if (cfg->forager == SF_FORAGER_ACCEPTED_COUNT && cfg->accepted_count_limit <= 0)
@@ -1652,6 +1660,9 @@ static void anneal_init_state(const sf_annealing_config& a, int levels, uint64_t
     w[SA_CALIBRATING] = a.mode == SF_ANNEAL_CALIBRATED ? 1 : 0;
 }
 
+static int tabu_phase_rows(sf_ctx* ctx, std::vector<uint64_t>& st);  // sf_api_tabu.inc
+static const char* tabu_launch_refusal(sf_ctx* ctx);
+
 // phase_started for every replica; replica r is seeded with seed + r
 static int anneal_phase_start(sf_ctx* ctx) {
     const sf_annealing_config& a = ctx->anneal;
@@ -1672,6 +1683,9 @@ static int anneal_phase_start(sf_ctx* ctx) {
             else
                 w[AX_PARAM] = ctx->sc_step_count_limit;
         }
+    // TabuSearch: its fixed words in the same rows, the memories in an arena reached through them (sf_tabu.h)
+    if (acceptor == SF_ACCEPT_TABU_SEARCH)
+        if (int rc = tabu_phase_rows(ctx, st)) return rc;
     HIPCHK(ctx, hipMemcpyAsync(p.sa.state, st.data(), st.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return SF_OK;
@@ -2015,6 +2029,13 @@ static int launch_search(sf_ctx* ctx, SearchParams& p, int grid, bool trace) {
     // GreatDeluge / StepCountingHillClimbing run in the TRACE instantiations of every engine (sf_step.h; with trace_replica = -1 nothing is
     // traced): the untraced kernels, which every other policy runs, hold none of their code
     trace = trace || p.acceptor == SF_ACCEPT_GREAT_DELUGE || p.acceptor == SF_ACCEPT_STEP_COUNTING_HILL_CLIMBING;
+    // TabuSearch likewise, at the sites that build move signatures (sf_tabu.h).  Its rows carry the address of the replica's arena: a phase
+    // that was not started under it has none
+    if (p.acceptor == SF_ACCEPT_TABU_SEARCH) {
+        if (ctx->sp.acceptor != SF_ACCEPT_TABU_SEARCH) return fail(ctx, SF_ERR_INVALID, "tabu search: sf_phase_start after the acceptor was configured");
+        if (const char* why = tabu_launch_refusal(ctx)) return fail(ctx, SF_ERR_UNSUPPORTED, why);
+        trace = true;
+    }
     // the 2-leaf nearby union has its own engines; every other union runs in the generic N-leaf engine
     // a configured root union (order / weights other than the default policy's) runs in the generic engine too
     bool nearby_scalar = false;  // the nearby scalar leaves live in the generic engine
@@ -2212,7 +2233,7 @@ int32_t sf_portfolio_migrate_local(sf_ctx* ctx, int32_t n_elite, int32_t n_repla
         return fail(ctx, SF_ERR_UNSUPPORTED, "elite migration: list-only models (the adopted state is the list class's best solution)");
     if (ctx->cfg.acceptor != SF_ACCEPT_HILL_CLIMBING && ctx->cfg.acceptor != SF_ACCEPT_LATE_ACCEPTANCE &&
         ctx->cfg.acceptor != SF_ACCEPT_DIVERSIFIED_LATE_ACCEPTANCE)  // every acceptor not listed is refused: an adopted solution has no place in its schedule
-        return fail(ctx, SF_ERR_UNSUPPORTED, "elite migration: HillClimbing / LateAcceptance / DiversifiedLateAcceptance (an annealing replica keeps a temperature schedule, a great deluge its water level, a step count its best step score)");
+        return fail(ctx, SF_ERR_UNSUPPORTED, "elite migration: HillClimbing / LateAcceptance / DiversifiedLateAcceptance (an annealing replica keeps a temperature schedule, a great deluge its water level, a step count its best step score, a tabu search its memories)");
     if (n_elite < 1 || n_replace < 0 || (int64_t)n_elite + n_replace > ctx->R)
         return fail(ctx, SF_ERR_INVALID, "elite migration: n_elite >= 1, n_replace >= 0, n_elite + n_replace <= replicas");
     if (out_adopted) *out_adopted = 0;
@@ -2407,3 +2428,4 @@ extern "C" int32_t sf_debug_phases(uint64_t* out8) {  // diagnostic builds only 
 #include "sf_candidate_trace.inc"
 #include "sf_api_anneal_debug.inc"
 #include "sf_api_acceptor_debug.inc"
+#include "sf_api_tabu.inc"

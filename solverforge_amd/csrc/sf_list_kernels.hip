@@ -1256,6 +1256,7 @@ __global__ __launch_bounds__(256) void k_list_phase_start(ListModel m, SearchPar
         p.has_best[r] = 1;
         acceptor_phase_started(p.acceptor, cur, p.sa.state + (size_t)r * SA_WORDS);  // GreatDeluge / StepCountingHillClimbing
     }
+    if (p.acceptor == 7) tabu_phase_started(p.sa.state + (size_t)r * SA_WORDS, cur, threadIdx.x, blockDim.x);  // TabuSearch: best, counters, the arena
 }
 
 // Elite migration inside one context (sf_portfolio_migrate_local; an extension, not in the reference): replica r with

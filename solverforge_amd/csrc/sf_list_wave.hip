@@ -1090,6 +1090,12 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
         [[maybe_unused]] bool thr_on = true;  // GreatDeluge / StepCountingHillClimbing (the TRACE instantiations carry them): their threshold of the step in `late` (sf_step.h)
         if constexpr (TRACE)
             if (acceptor == 5 || acceptor == 6) ax_step_begin<L>(acceptor, p.sa.state + (size_t)r * SA_WORDS, late, thr_on);
+        // TabuSearch (the TRACE instantiations carry it too): the memories and the acceptor's best as they stand at step begin -- nothing changes
+        // them before tabu_step_ended (sf_tabu.h).  One scope: the list variable; entities are routes, values element ids.
+        [[maybe_unused]] TabuStep<L> tabu;
+        [[maybe_unused]] const TabuScope tabu_scope{0u, 0u, 0u};
+        if constexpr (TRACE)
+            if (acceptor == 7) tabu_step_begin<L>(p.sa.state + (size_t)r * SA_WORDS, tabu);
         int has_best = 0;
         typename std::conditional<SMALL, uint32_t, uint64_t>::type equal_count = 0;  // (SMALL: 32 bits -- a step consumes far fewer than 2^32 candidates; reservoir_pick hashes it as 64 bits)
         uint32_t accepted = 0, pulls = 0;
@@ -1783,6 +1789,19 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                     }
                     if constexpr (TRACE)
                         if (acceptor == 5 || acceptor == 6) acc = ax_accepts<L>(doable, sc, curv, late, thr_on);
+                    if constexpr (TRACE)
+                        if (acceptor == 7) {  // the candidate's signature from the working lists, which no candidate of the step has changed
+                            TabuSig sig{{TABU_NO_TOKEN, TABU_NO_TOKEN}, {TABU_NO_TOKEN, TABU_NO_TOKEN}, {0, 0}, {0, 0}};
+                            if (doable) {  // (a doable move's positions lie inside their lists)
+                                const uint32_t a = m0 >> 16, i = m0 & 0xFFFFu, b = m1 >> 16, j = m1 & 0xFFFFu;
+                                const uint32_t u = ext_id(s_visits[s_off[a] + i]);
+                                if (lf ? chg1 : chg0)  // j is the destination before the removal (apply_list_move_wave): adjusted_destination, change.rs:28-34
+                                    tabu_sig_list_change(tabu_scope, a, i, b, (a == b && j > i) ? j - 1 : j, u, sig);
+                                else
+                                    tabu_sig_list_swap(tabu_scope, a, i, u, b, j, ext_id(s_visits[s_off[b] + j]), sig);
+                            }
+                            acc = tabu_accepts<L>(tabu, doable, sc, sig);
+                        }
                     SaChunk sach;
                     if constexpr (!FAST)
                         if (annealing) acc = sa_decide<L>(saw, p.sa, doable, sc, curv, lane, sach);
@@ -1903,6 +1922,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
             for (int kk = 0; kk < L; ++kk) best.v[kk] = wadd(cur[kk], (int64_t)best_d[kk]);
         }
         const bool applied = has_best && !dry_run;
+        [[maybe_unused]] TabuSig pick_sig;  // TabuSearch: the pick's signature, taken before the commit writes the lists
         if (applied) {
             if (best_pending) {
                 ScoreV<L> bs;
@@ -1943,6 +1963,14 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                 }
                 nsat = uni(nsat);  // (the move's kind comes out of a shuffle: say that the count is wave-uniform, so the pass branches on a scalar)
             }
+            if constexpr (TRACE)
+                if (acceptor == 7) {
+                    const uint32_t u = ext_id(s_visits[s_off[a] + i]);
+                    if (kind == 2)
+                        tabu_sig_list_change(tabu_scope, a, i, b, (a == b && j > i) ? j - 1 : j, u, pick_sig);
+                    else
+                        tabu_sig_list_swap(tabu_scope, a, i, u, b, j, ext_id(s_visits[s_off[b] + j]), pick_sig);
+                }
             apply_list_move_wave<LT, OT, RANKTAB && L == 4>(m, s_visits, s_off, s_load, kind, a, i, b, j);  // (the four-level COMPACT kernels: one register short without it)
             {  // refresh node -> (route, position) for the two touched routes
                 const uint32_t oa = s_off[a], la = s_off[a + 1] - oa;
@@ -1999,6 +2027,8 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
             }
             if constexpr (TRACE)
                 if (acceptor == 5 || acceptor == 6) ax_step_ended<L>(acceptor, lane == 0, cur, p.sa.state + (size_t)r * SA_WORDS);
+            if constexpr (TRACE)
+                if (acceptor == 7) tabu_step_ended<L>(p.sa.state + (size_t)r * SA_WORDS, lane == 0, cur, applied ? &pick_sig : nullptr);
             if constexpr (!FAST)
                 if (annealing) sa_step_ended(saw, p.sa, lane);
             wave_sync();

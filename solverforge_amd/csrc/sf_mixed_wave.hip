@@ -337,6 +337,28 @@ constexpr size_t SF_MIXED_PREC_STATIC_LDS = SF_MIXED_STATIC_LDS + 64 + 32 + 64;
 #ifndef SF_MIXED_PREC_BLOCKS_PER_CU
 #define SF_MIXED_PREC_BLOCKS_PER_CU 4
 #endif
+// TabuSearch (sf_tabu.h): the signature of a candidate of leaf kind 1 / 2 (scalar change / swap; the nearby scalar leaves emit the same moves) or
+// 4 / 16 (list change) / 8 / 32 (list swap) from its ring words and the working state BEFORE the move.  Two scopes in a mixed model: the scalar
+// class's variable first, then the list variable -- an entity index of one and an equal route index of the other are different tokens.
+// List change: the second word's position is the destination before the removal (apply_list_move_wave); the identity takes
+// adjusted_destination (list_kernel/change.rs:28-34).
+template <class VT, class OT>
+__device__ __forceinline__ void tabu_sig_generic(int kind, uint32_t c0, uint32_t c1, const VT* s_vals, const uint16_t* s_visits, const OT* s_off,
+                                                 const TabuScope& scalar_scope, const TabuScope& list_scope, TabuSig& sig) {
+    if (kind == 1) {
+        tabu_sig_change(scalar_scope, c0, (int32_t)s_vals[c0], (int32_t)c1, sig);
+    } else if (kind == 2) {
+        tabu_sig_swap(scalar_scope, c0, c1, (int32_t)s_vals[c0], (int32_t)s_vals[c1], sig);
+    } else {
+        const uint32_t a = c0 >> 16, i = c0 & 0xFFFFu, b = c1 >> 16, j = c1 & 0xFFFFu;
+        const uint32_t u = (uint32_t)s_visits[(uint32_t)s_off[a] + i];
+        if (kind == 4 || kind == 16)
+            tabu_sig_list_change(list_scope, a, i, b, (a == b && j > i) ? j - 1 : j, u, sig);
+        else
+            tabu_sig_list_swap(list_scope, a, i, u, b, j, (uint32_t)s_visits[(uint32_t)s_off[b] + j], sig);
+    }
+}
+
 template <int L, bool TRACE, class VT, bool RUIN = false, bool PREC = false, int MODE = 0>
 // the FAST kernels without a ruin leaf keep their node -> slot table in HBM too (1) or in the LDS slice (0)
 #ifndef SF_MIXED_FAST_NODEG
@@ -1058,6 +1080,12 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
         [[maybe_unused]] bool thr_on = true;  // GreatDeluge / StepCountingHillClimbing (the TRACE instantiations carry them): their threshold of the step in `late` (sf_step.h)
         if constexpr (TRACE)
             if (acceptor == 5 || acceptor == 6) ax_step_begin<L>(acceptor, p.sa.state + (size_t)r * SA_WORDS, late, thr_on);
+        // TabuSearch (the TRACE instantiations carry it too): the memories and the acceptor's best as they stand at step begin (sf_tabu.h)
+        [[maybe_unused]] TabuStep<L> tabu;
+        [[maybe_unused]] const TabuScope tabu_scalar_scope{0u, 0u, 0u};
+        [[maybe_unused]] const TabuScope tabu_list_scope{has_scalar ? 1u : 0u, has_scalar ? (uint32_t)sm.n : 0u, has_scalar ? (uint32_t)sm.n_values + 1u : 0u};
+        if constexpr (TRACE)
+            if (acceptor == 7) tabu_step_begin<L>(p.sa.state + (size_t)r * SA_WORDS, tabu);
         int has_best = 0;
         uint64_t equal_count = 0;
         uint32_t accepted = 0;
@@ -2543,6 +2571,12 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                 }
                 if constexpr (TRACE)
                     if (acceptor == 5 || acceptor == 6) acc = ax_accepts<L>(consult, sc, curv, late, thr_on);
+                if constexpr (TRACE)
+                    if (acceptor == 7) {  // (the host admits leaf kinds 1, 2, 2048, 4096, 4, 8, 16, 32 only; a doable move's positions lie inside their lists)
+                        TabuSig sig{{TABU_NO_TOKEN, TABU_NO_TOKEN}, {TABU_NO_TOKEN, TABU_NO_TOKEN}, {0, 0}, {0, 0}};
+                        if (consult) tabu_sig_generic(my_kind, m0, m1, s_vals, s_visits, s_off, tabu_scalar_scope, tabu_list_scope, sig);
+                        acc = tabu_accepts<L>(tabu, consult, sc, sig);
+                    }
                 SaChunk sach;
                 if (annealing) acc = sa_decide<L>(saw, p.sa, consult, sc, curv, lane, sach);
                 uint64_t accmask = __ballot(acc);
@@ -2685,6 +2719,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
             for (uint32_t t = lane; t < ns; t += 64) sm.best_vals[(size_t)r * ns + t] = (int32_t)s_vals[t];
         };
         const bool applied = has_best && !dry_run;
+        [[maybe_unused]] TabuSig pick_sig;  // TabuSearch: the pick's signature, taken before the commit writes the values / the lists
         if (applied) {
             if (best_pending) {
                 ScoreV<L> bs;
@@ -2698,6 +2733,8 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
             int kind = lt.geti(uni((uint32_t)best_leaf), LeafTab::KIND);
             if (!FAST) kind = kind == 2048 ? 1 : (kind == 4096 ? 2 : kind);
             const uint32_t a = uni(best_m0), b = uni(best_m1);
+            if constexpr (TRACE)
+                if (acceptor == 7) tabu_sig_generic(kind, a, b, s_vals, s_visits, s_off, tabu_scalar_scope, tabu_list_scope, pick_sig);
             if (!FAST && kind <= 2) {
                 if (tracing && lane == 0) {
                     p.trace_applied[0] = 1;
@@ -2865,6 +2902,8 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
             }
             if constexpr (TRACE)
                 if (acceptor == 5 || acceptor == 6) ax_step_ended<L>(acceptor, lane == 0, cur, p.sa.state + (size_t)r * SA_WORDS);
+            if constexpr (TRACE)
+                if (acceptor == 7) tabu_step_ended<L>(p.sa.state + (size_t)r * SA_WORDS, lane == 0, cur, applied ? &pick_sig : nullptr);
             if (annealing) sa_step_ended(saw, p.sa, lane);
             wave_sync();
             st_steps += 1;

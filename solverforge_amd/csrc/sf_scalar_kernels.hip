@@ -1419,6 +1419,7 @@ __global__ __launch_bounds__(256) void k_scalar_phase_start(ScalarModel m, Searc
         p.has_best[r] = 1;
         acceptor_phase_started(p.acceptor, cur, p.sa.state + (size_t)r * SA_WORDS);  // GreatDeluge / StepCountingHillClimbing
     }
+    if (p.acceptor == 7) tabu_phase_started(p.sa.state + (size_t)r * SA_WORDS, cur, threadIdx.x, blockDim.x);  // TabuSearch: best, counters, the arena
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1588,6 +1589,12 @@ __global__ __launch_bounds__(64 * 4, SF_SCALAR_BLOCKS_PER_CU) void k_scalar_sear
         [[maybe_unused]] bool thr_on = true;  // GreatDeluge / StepCountingHillClimbing (the TRACE instantiations carry them): their threshold of the step in `late` (sf_step.h)
         if constexpr (TRACE)
             if (p.acceptor == 5 || p.acceptor == 6) ax_step_begin<L>(p.acceptor, p.sa.state + (size_t)r * SA_WORDS, late, thr_on);
+        // TabuSearch (the TRACE instantiations carry it too): the memories and the acceptor's best as they stand at step begin -- nothing changes
+        // them before tabu_step_ended (sf_tabu.h).  One scope: the class's one planning variable.
+        [[maybe_unused]] TabuStep<L> tabu;
+        [[maybe_unused]] const TabuScope tabu_scope{0u, 0u, 0u};
+        if constexpr (TRACE)
+            if (p.acceptor == 7) tabu_step_begin<L>(p.sa.state + (size_t)r * SA_WORDS, tabu);
         int has_best = 0;
         uint64_t equal_count = 0;
         uint32_t accepted = 0, pulls = 0;
@@ -1795,6 +1802,15 @@ __global__ __launch_bounds__(64 * 4, SF_SCALAR_BLOCKS_PER_CU) void k_scalar_sear
                 }
                 if constexpr (TRACE)
                     if (p.acceptor == 5 || p.acceptor == 6) acc = ax_accepts<L>(doable, sc, curv, late, thr_on);
+                if constexpr (TRACE)
+                    if (p.acceptor == 7) {  // the candidate's signature from the working values, which no candidate of the step has changed
+                        TabuSig sig;
+                        if (lane_change)
+                            tabu_sig_change(tabu_scope, m0, (int32_t)s_vals[m0], (int32_t)m1, sig);
+                        else
+                            tabu_sig_swap(tabu_scope, m0, m1, (int32_t)s_vals[m0], (int32_t)s_vals[m1], sig);
+                        acc = tabu_accepts<L>(tabu, doable, sc, sig);
+                    }
                 SaChunk sach;
                 if (annealing) acc = sa_decide<L>(saw, p.sa, doable, sc, curv, lane, sach);
                 uint64_t accmask = __ballot(acc);
@@ -1892,6 +1908,7 @@ __global__ __launch_bounds__(64 * 4, SF_SCALAR_BLOCKS_PER_CU) void k_scalar_sear
 
         // ---- commit the forager's pick ----
         const bool applied = has_best && !p.dry_run;
+        [[maybe_unused]] TabuSig pick_sig;  // TabuSearch: the pick's signature, taken before the commit writes the values
         if (applied) {
             if (best_pending) {
                 ScoreV<L> bs;
@@ -1904,6 +1921,13 @@ __global__ __launch_bounds__(64 * 4, SF_SCALAR_BLOCKS_PER_CU) void k_scalar_sear
             }
             const bool pick_change = best_leaf ? chg1 : chg0;
             const uint32_t a = uni(best_m0), b = uni(best_m1);
+            if constexpr (TRACE)
+                if (p.acceptor == 7) {
+                    if (pick_change)
+                        tabu_sig_change(tabu_scope, a, (int32_t)s_vals[a], (int32_t)b, pick_sig);
+                    else
+                        tabu_sig_swap(tabu_scope, a, b, (int32_t)s_vals[a], (int32_t)s_vals[b], pick_sig);
+                }
             if (tracing && lane == 0) {
                 p.trace_applied[0] = 1;
                 if ((int64_t)best_ti < p.trace_cap) p.trace_flags[best_ti] |= 4;  // Selected + Applied
@@ -1965,6 +1989,8 @@ __global__ __launch_bounds__(64 * 4, SF_SCALAR_BLOCKS_PER_CU) void k_scalar_sear
             }
             if constexpr (TRACE)
                 if (p.acceptor == 5 || p.acceptor == 6) ax_step_ended<L>(p.acceptor, lane == 0, cur, p.sa.state + (size_t)r * SA_WORDS);
+            if constexpr (TRACE)
+                if (p.acceptor == 7) tabu_step_ended<L>(p.sa.state + (size_t)r * SA_WORDS, lane == 0, cur, applied ? &pick_sig : nullptr);
             if (annealing) sa_step_ended(saw, p.sa, lane);
             wave_sync();
             st_steps += 1;

@@ -12,7 +12,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import (ACCEPTOR_RECORD_DTYPE, ACCEPTOR_STATE_WORDS, ANNEAL_CHUNK_DTYPE, ANNEAL_STATE_WORDS, MOVE_DTYPE, AnnealingConfigStruct, ScalarConstructionConfigStruct, SolverConfigStruct, SolverForgeError, StatsStruct,
+from ._lib import (ACCEPTOR_RECORD_DTYPE, ACCEPTOR_STATE_WORDS, ANNEAL_CHUNK_DTYPE, ANNEAL_STATE_WORDS, MOVE_DTYPE, TABU_MAX_TENURE_MOVE, TABU_RECORD_DTYPE, TABU_STATE_FIXED, AnnealingConfigStruct,
+                   ScalarConstructionConfigStruct, SolverConfigStruct, SolverForgeError, StatsStruct, TabuConfigStruct,
                    check, ptr)
 
 
@@ -42,6 +43,7 @@ class Acceptor:
     DIVERSIFIED_LATE_ACCEPTANCE = 4  # default of grouped scalar-only models (default_local_search/policy.rs:52-55)
     GREAT_DELUGE = 5  # great_deluge.rs:89-129; configure_great_deluge
     STEP_COUNTING_HILL_CLIMBING = 6  # step_counting.rs:85-129; configure_step_counting
+    TABU_SEARCH = 7  # tabu_search.rs:64-237; configure_tabu (scalar, nearby scalar, list and nearby list change / swap leaves; scalar, wave and generic engines)
 
 
 class AnnealingMode:
@@ -624,6 +626,53 @@ class GpuScoreDirector:
         accept = np.zeros(max(n, 1), dtype=np.uint64)
         state = np.zeros((max(n, 1), ACCEPTOR_STATE_WORDS), dtype=np.uint64)
         check(self._L.sf_debug_acceptor_script(self._h, int(acceptor), levels, bits, n, ptr(records), ptr(accept), ptr(state)), self._h)
+        return accept[:n], state[:n]
+
+    @staticmethod
+    def _tabu_config(entity_tabu_size, value_tabu_size, move_tabu_size, undo_move_tabu_size, aspiration_enabled):
+        size = lambda v: -1 if v is None else int(v)  # noqa: E731
+        return TabuConfigStruct(size(entity_tabu_size), size(value_tabu_size), size(move_tabu_size), size(undo_move_tabu_size), 1 if aspiration_enabled else 0, 0)
+
+    def configure_tabu(self, entity_tabu_size=None, value_tabu_size=None, move_tabu_size=None, undo_move_tabu_size=None, aspiration_enabled=True):
+        """Policy of Acceptor.TABU_SEARCH (TabuSearchPolicy, tabu_search.rs:12-55; builder/acceptor.rs:383-405); takes effect at the next
+        phase_start.  None = the dimension is absent; all four absent = move-only 10; an explicit 0 is refused with the reference's
+        message; move / undo tenures above 64 are unsupported.  Call it before configure(SolverConfig(acceptor=Acceptor.TABU_SEARCH)):
+        the kind is taken only once its policy was set (configure_tabu() with no argument sets the default)."""
+        cfg = self._tabu_config(entity_tabu_size, value_tabu_size, move_tabu_size, undo_move_tabu_size, aspiration_enabled)
+        check(self._L.sf_solver_configure_tabu(self._h, C.byref(cfg)), self._h)
+
+    def tabu_state(self, replica=0):
+        """TabuSearch state of one replica: dict of best (int64[levels], the acceptor's own best step score), pushes (4 ints: entity,
+        value, move, undo), entity / value (the tokens currently tabu, ascending: entity index; value index + 1, 0 = None), moves / undo
+        (the live identities oldest to newest, (word0, word1) tuples in the device packing)."""
+        best, pushes = np.zeros(4, dtype=np.int64), np.zeros(4, dtype=np.uint64)
+        mv, un = np.zeros(2 * TABU_MAX_TENURE_MOVE, dtype=np.uint64), np.zeros(2 * TABU_MAX_TENURE_MOVE, dtype=np.uint64)
+        n_mv, n_un, n_e, n_v = C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        cap_e = cap_v = 64
+        while True:
+            ent, val = np.zeros(cap_e, dtype=np.uint32), np.zeros(cap_v, dtype=np.uint32)
+            check(self._L.sf_get_tabu_state(self._h, replica, ptr(best), ptr(pushes), cap_e, ptr(ent), C.byref(n_e), cap_v, ptr(val), C.byref(n_v),
+                                            ptr(mv), C.byref(n_mv), ptr(un), C.byref(n_un)), self._h)
+            if n_e.value <= cap_e and n_v.value <= cap_v:
+                break
+            cap_e, cap_v = max(cap_e, n_e.value), max(cap_v, n_v.value)
+        pairs = lambda a, n: [(int(a[2 * k]), int(a[2 * k + 1])) for k in range(n)]  # noqa: E731
+        return {"best": best[:self.levels].copy(), "pushes": [int(x) for x in pushes], "entity": [int(x) for x in ent[:n_e.value]],
+                "value": [int(x) for x in val[:n_v.value]], "moves": pairs(mv, n_mv.value), "undo": pairs(un, n_un.value)}
+
+    def debug_tabu_script(self, records, n_entity_ids, n_value_ids, levels=1, entity_tabu_size=None, value_tabu_size=None, move_tabu_size=None,
+                          undo_move_tabu_size=None, aspiration_enabled=True):
+        """sf_debug_tabu_script: the engines' TabuSearch code (csrc/sf_tabu.h) alone on a scripted sequence.  records: array of
+        TABU_RECORD_DTYPE (score[4], sc[64][4], sig[64] in the device packing, reach mask, op 0 phase_started / 1 decide / 2 step_ended,
+        has_sig), the first one a phase start.  Returns (accept masks u64[n], state u64[n, 16 + n_entity_ids + n_value_ids + 256] after
+        every record: best[4], pushes[4], tenures[4], aspiration, 3 zeros, entity stamps, value stamps, move ring, undo ring)."""
+        records = np.ascontiguousarray(records, dtype=TABU_RECORD_DTYPE)
+        n = len(records)
+        cfg = self._tabu_config(entity_tabu_size, value_tabu_size, move_tabu_size, undo_move_tabu_size, aspiration_enabled)
+        width = TABU_STATE_FIXED + n_entity_ids + n_value_ids + 4 * TABU_MAX_TENURE_MOVE
+        accept = np.zeros(max(n, 1), dtype=np.uint64)
+        state = np.zeros((max(n, 1), max(width, 1)), dtype=np.uint64)
+        check(self._L.sf_debug_tabu_script(self._h, C.byref(cfg), levels, n_entity_ids, n_value_ids, n, ptr(records), ptr(accept), ptr(state)), self._h)
         return accept[:n], state[:n]
 
     def annealing_state(self, replica=0):
