@@ -224,6 +224,17 @@ def ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def nbr_facts(keys):
+    """sf_debug_nbr_facts (diagnostic, not in the ABI header): (tie_max, rows_full) of a neighbour index given as a [rows, dim] uint16 array --
+    the widest run of entries that share a distance, saturated at 64, and whether every row has min(dim, 64) finite entries."""
+    a = np.ascontiguousarray(keys, dtype=np.uint16)
+    out = (C.c_int32 * 2)()
+    fn = C.CDLL(LIB_PATH).sf_debug_nbr_facts
+    fn.restype = C.c_int32
+    check(fn(ptr(a), a.shape[0], a.shape[1], out, 2))
+    return int(out[0]), int(out[1])
+
+
 def check(rc, ctx=None):
     if rc == SF_OK:
         return

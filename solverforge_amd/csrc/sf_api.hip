@@ -22,6 +22,7 @@
 #include "sf_kopt_tw.hip"
 #include "sf_precedence.hip"
 #include "sf_scalar_construct.h"
+#include "sf_nbr_facts.h"  // NbrFacts / nbr_facts_rows: what holds of the neighbour index for the life of the context
 
 using namespace sf;
 
@@ -115,11 +116,12 @@ struct sf_ctx {
     bool prec_policy = false;  // sf_list_set_precedence_policy
     PlfModel plf{};  // critical-path precedence leaf: per-replica tables (allocated at the first launch that has the leaf)
     NbrIndex nbr{nullptr};  // presorted neighbour index (wave engine)
+    NbrFacts nbr_facts{};   // ... and its tie structure (either numbering: renumbering keeps every row's flags in place)
     ListModel lm_wave{};          // the list model as the COMPACT wave kernel sees it when the nodes are renumbered (ListModel::perm)
     NbrIndex nbr_wave{nullptr};   // ... and its neighbour index
     bool wave_renumbered = false;
     int last_wave_mode = -1;      // launch mode of the last wave-engine launch (sf_list_wave_layout)
-    int32_t wave_spec_state = 0, wave_spec_reason = 0, wave_spec_key[18] = {};  // ... and whether it ran the kernel compiled for this context's constants (sf_debug_wave_spec)
+    int32_t wave_spec_state = 0, wave_spec_reason = 0, wave_spec_key[22] = {};  // ... and whether it ran the kernel compiled for this context's constants (sf_debug_wave_spec)
     int n_cus = 0;                // CUs of the device (read at the first wave launch)
     int32_t last_generic_flags = -1;  // what the last generic-engine launch took (sf_list_arith_flags)
     int32_t last_scalar_value_bytes = 0;  // value-type bytes of the last scalar-engine launch (sf_list_arith_flags)
@@ -1054,6 +1056,17 @@ static int build_list_model(sf_ctx* ctx, int d) {
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         ctx->nbr = NbrIndex{keys};
+        // the index's facts (sf_nbr_facts.h), once: a host pass over the index as it comes down, at most 4 Mi entries at a time
+        NbrFacts nf{0, 1};
+        const int64_t rows_per = std::max<int64_t>(1, ((int64_t)4 << 20) / m.dim);
+        std::vector<uint16_t> part((size_t)std::min<int64_t>(rows_per, m.dim) * m.dim);
+        for (int64_t r0 = 0; r0 < m.dim; r0 += rows_per) {
+            const int64_t n = std::min<int64_t>(rows_per, m.dim - r0);
+            HIPCHK(ctx, hipMemcpyAsync(part.data(), keys + (size_t)r0 * m.dim, (size_t)n * m.dim * 2, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            nbr_facts_rows(part.data(), n, m.dim, nf);
+        }
+        ctx->nbr_facts = nf;
     }
     // Internal node numbering for the COMPACT wave kernel (ListModel::perm): once the u16 matrix and the neighbour index outgrow an
     // XCD's 4 MiB L2, every 2-byte leg gather pulls its own line from the Infinity Cache / HBM (CVRP-5000: 352 B of memory-side traffic
@@ -1252,7 +1265,7 @@ static int launch_list_wave(sf_ctx* ctx, const SearchParams& p, int n_replicas, 
     // the kernel compiled for this context's constants, when the policy wants it and it can be had; else the ahead-of-time one
     if (!ctx->n_cus) HIPCHK(ctx, hipDeviceGetAttribute(&ctx->n_cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
     const WaveSpecGate gate{pl.mode, q.move_budget != 0, (int32_t)std::min<int64_t>(std::max<int64_t>(q.n_steps, 0), INT32_MAX), n_replicas, pl.resident, ctx->n_cus, wave_spec_knob()};
-    const WaveSpecKey key = wave_spec_key(pl.levels, pl.wpe, *la.lm, q, wave_spec_extras());
+    const WaveSpecKey key = wave_spec_key(pl.levels, pl.wpe, *la.lm, q, ctx->nbr_facts, wave_spec_extras());
     ctx->wave_spec_state = SF_WSPEC_AOT, ctx->wave_spec_reason = wave_spec_wanted(gate);
     std::memcpy(ctx->wave_spec_key, &key, sizeof key);
     if (ctx->wave_spec_reason == SF_WSPEC_R_NONE) {
@@ -2338,12 +2351,13 @@ extern "C" int32_t sf_debug_wave_plan(const int32_t* shape, int32_t n_shape, con
 
 // The run-time specialisation of the wave engine (sf_wave_spec.h; tests/test_wave_spec.py, tests/test_gpu_wave_spec.py).
 // sf_debug_wave_spec: out[0] state of the context's last wave launch (0 ahead-of-time, 1 specialised, 2 fell back), out[1] its reason code
-// (SF_WSPEC_R_*), out[2] compiles of the process, out[3] the last compile's milliseconds (rounded up), out[4..] the key (WaveSpecKey, 18 words).
-// `ctx` may be null: the process-wide figures alone.
+// (SF_WSPEC_R_*), out[2] compiles of the process, out[3] the last compile's milliseconds (rounded up), out[4..] the key (WaveSpecKey: 22 words,
+// or its first 18 -- the key without the index's facts and their candidates).  `ctx` may be null: the process-wide figures alone.
 extern "C" int32_t sf_debug_wave_spec(const sf_ctx* ctx, int32_t* out, int32_t n_out) {
-    if (!out || n_out != 4 + (int)(sizeof(WaveSpecKey) / 4)) return SF_ERR_INVALID;
+    static_assert(sizeof(WaveSpecKey) == sizeof(sf_ctx::wave_spec_key), "WaveSpecKey");
+    if (!out || (n_out != 4 + (int)(sizeof(WaveSpecKey) / 4) && n_out != 4 + SF_WSPEC_KEY_WORDS_V1)) return SF_ERR_INVALID;
     std::memset(out, 0, (size_t)n_out * 4);
-    if (ctx) out[0] = ctx->wave_spec_state, out[1] = ctx->wave_spec_reason, std::memcpy(out + 4, ctx->wave_spec_key, sizeof(WaveSpecKey));
+    if (ctx) out[0] = ctx->wave_spec_state, out[1] = ctx->wave_spec_reason, std::memcpy(out + 4, ctx->wave_spec_key, (size_t)(n_out - 4) * 4);
     WaveSpecCache& c = wave_spec_cache();
     std::lock_guard<std::mutex> lock(c.mu);
     out[2] = c.compiles, out[3] = (int32_t)std::ceil(c.last_ms);
@@ -2366,13 +2380,28 @@ extern "C" int32_t sf_debug_wave_spec_gate(const int32_t* gate, int32_t n_gate) 
     std::memcpy(&g, gate, sizeof g);
     return wave_spec_wanted(g);
 }
+// The facts of a neighbour index given as a host array of rows x dim u16 entries (sf_nbr_facts.h; tests/test_wave_index_facts.py): out[0] the
+// widest run of entries that share a distance, saturated at 64; out[1] whether every row has min(dim, 64) finite entries.  No device, no context.
+extern "C" int32_t sf_debug_nbr_facts(const uint16_t* keys, int32_t rows, int32_t dim, int32_t* out, int32_t n_out) {
+    if (!keys || !out || rows < 1 || dim < 1 || n_out != 2) return SF_ERR_INVALID;
+    NbrFacts f{0, 1};
+    nbr_facts_rows(keys, rows, dim, f);
+    out[0] = f.tie_max, out[1] = f.rows_full;
+    return SF_OK;
+}
+// The index candidates' gate on flat words: in = V, dim, n_cap, tie_max, rows_full (facts as sf_debug_nbr_facts gives them).  Returns the
+// SF_WSPEC_X_* bits a key of these constants and facts may compile in.
+extern "C" int32_t sf_debug_wave_spec_index_gate(const int32_t* in, int32_t n_in) {
+    if (!in || n_in != 5 || in[0] < 1 || in[1] < 1 || in[2] < 0) return SF_ERR_INVALID;
+    return wave_spec_index_allowed(WaveSpecIndexGate{in[0], in[1], in[2], in[3] >= 64, in[3] >= 2, in[4] != 0});
+}
 // One compile of the specialised unit for `arch` without a device: the option list (one option per line) into `opts`, the code object into the
 // file `out_path` (when given).  Returns the build's reason code (SF_WSPEC_R_NONE = compiled); `ms` receives the compile's milliseconds, `log`
 // the compiler's log.
 extern "C" int32_t sf_debug_wave_spec_compile(const int32_t* key, int32_t n_key, const char* arch, const char* out_path, char* opts, int32_t n_opts, char* log, int32_t n_log, double* ms) {
-    if (!key || n_key * 4 != (int)sizeof(WaveSpecKey) || !arch) return SF_ERR_INVALID;
-    WaveSpecKey k;
-    std::memcpy(&k, key, sizeof k);
+    if (!key || (n_key * 4 != (int)sizeof(WaveSpecKey) && n_key != SF_WSPEC_KEY_WORDS_V1) || !arch) return SF_ERR_INVALID;
+    WaveSpecKey k{};  // (18 words: no facts of the index, none of their candidates)
+    std::memcpy(&k, key, (size_t)n_key * 4);
     if (!wave_spec_key_ok(k)) return SF_ERR_INVALID;
     const std::string csrc = wave_spec_csrc();
     auto put = [](char* dst, int32_t n, const std::string& s) {

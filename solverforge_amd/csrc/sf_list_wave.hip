@@ -79,6 +79,30 @@ constexpr int WPB = SF_WPB;  // waves (= replicas) per workgroup
 #else
 #define SF_SPEC_OWN_LANE(v)
 #endif
+// Facts of the neighbour index, fixed like the constants above once sf_initialize has built it (sf_nbr_facts.h).
+// The run-time unit may be compiled for them; every macro is the identity in the shipped library.
+//   SF_SPEC_NO_WIDE    no equal-distance group has 64 members: gen_rest's serial top-k over the rest of a row is never reached
+//   SF_SPEC_NO_TIES    no two entries of a row share a distance: no group has a second member, the inversion correction has nothing to do
+//   SF_SPEC_ROWS_FULL  every row has min(dim, 64) finite entries and dim >= 32: no lane of the paired pass is past its row
+//   SF_SPEC_TIE_KEY    (with SF_SPEC_RB = bits that hold V - 1, SF_SPEC_PB = bits that hold n_cap, RB + PB <= 22) the inversion correction
+//                      compares one packed word per lane (tie_key_fix below); an inter-list ordinal is 1 << (RB + PB) | rank << PB | position
+#ifdef SF_SPEC_NO_WIDE
+#define SF_SPEC_WIDE_TIES(x) false
+#else
+#define SF_SPEC_WIDE_TIES(x) (x)
+#endif
+#ifdef SF_SPEC_NO_TIES
+#define SF_SPEC_TIES(x) 0ULL
+#else
+#define SF_SPEC_TIES(x) (x)
+#endif
+#ifdef SF_SPEC_ROWS_FULL
+#define SF_SPEC_ROW_HAVE(x) true
+#define SF_SPEC_ROW_HAVEMASK(x) (~0ULL)
+#else
+#define SF_SPEC_ROW_HAVE(x) (x)
+#define SF_SPEC_ROW_HAVEMASK(x) (x)
+#endif
 
 
 // wavefront-scope ordering of LDS/global traffic between lanes of one wave (no instruction cost:
@@ -279,7 +303,15 @@ struct RouteTab {
     __device__ __forceinline__ static uint32_t rank(uint32_t w) { return w & 0xFFFFu; }
     __device__ __forceinline__ static uint32_t inter_ord(uint32_t w, uint32_t dp) { return ORD_INTER_BASE + (w >> 16) + dp; }
 };
+#ifdef SF_SPEC_TIE_KEY
+// the same order in the fewest bits (positions <= n_cap < 2^PB, ranks <= V - 1 < 2^RB): an ordinal stays below 2^(RB + PB + 1) <= 2^23
+static_assert(SF_SPEC_RB >= 1 && SF_SPEC_PB >= 1 && SF_SPEC_RB + SF_SPEC_PB <= 22, "SF_SPEC_TIE_KEY: the packed word does not fit 32 bits");
+constexpr uint32_t ORD_ARITH_BASE = 1u << (SF_SPEC_RB + SF_SPEC_PB);
+constexpr int ORD_ARITH_SHIFT = SF_SPEC_PB;
+#else
 constexpr uint32_t ORD_ARITH_BASE = 1u << 26;  // above every intra-list ordinal (a position, < 2^16); rank << 16 | position stays below 2^27
+constexpr int ORD_ARITH_SHIFT = 16;
+#endif
 struct RouteArith {
     uint32_t st, inv, V, recip;  // permutation start, stride^-1 mod V, V, floor(2^32 / V) (V <= 1022: every product below stays under 2^21)
     static constexpr int KEY_SHIFT = 28;  // (the legs of a COMPACT kernel are < 2^26)
@@ -291,7 +323,7 @@ struct RouteArith {
         return rk >= V ? rk - V : rk;
     }
     __device__ __forceinline__ static uint32_t rank(uint32_t w) { return w; }
-    __device__ __forceinline__ static uint32_t inter_ord(uint32_t w, uint32_t dp) { return ORD_ARITH_BASE + (w << 16) + dp; }
+    __device__ __forceinline__ static uint32_t inter_ord(uint32_t w, uint32_t dp) { return ORD_ARITH_BASE + (w << ORD_ARITH_SHIFT) + dp; }
 };
 struct RouteRank {  // RouteTab's table holding the rank alone, RouteArith's ordinals
     const uint32_t* rt;
@@ -333,6 +365,32 @@ __device__ __forceinline__ NearbyItem nearby_item_rt(bool is_change, uint32_t sl
 __device__ __forceinline__ uint32_t mbcnt64(uint64_t mask) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
+#ifdef SF_SPEC_TIE_KEY
+// The inversion correction of a lane's sorted position inside its equal-distance group on ONE packed word per lane,
+//   Q = group << (RB + PB + 3) | ordinal << 2 | weight,
+// `group` = the group starts in lanes 1 .. lane (the inclusive count less lane 0's own bit in every lane alike; <= 63).  It never decreases
+// with the lane, so "the lane d away is in my group" and "its ordinal is on the other side of mine" are one unsigned compare: the lane d
+// above (a later row entry) precedes me exactly when its Q is below mine, the lane d below follows me exactly when its Q is above mine.  What
+// is added is the OTHER lane's weight, so a lane past the wave (bound_ctrl: Q = 0), a lane past the row, a lane of the group still open and
+// a lane whose node is unassigned -- whose ordinal may be anything, the group field included -- add zero, and what such a lane works out for
+// itself is never stored.  Lanes of non-zero weight in one group never share an ordinal (they address distinct slots), so equal ordinals
+// only meet a zero weight.  `nonstart` = the closed lanes that continue the group of the lane before; the trip count is the widest closed
+// group's width less one, by the wave-uniform recurrence of the general form.
+__device__ __forceinline__ int32_t tie_key_fix(uint64_t startmask, uint64_t nonstart, uint32_t ord, uint32_t wc) {
+    const uint32_t q = (mbcnt64(startmask >> 1) << (SF_SPEC_RB + SF_SPEC_PB + 3)) | (ord << 2) | wc;
+    uint32_t q_dn = q, q_up = q;
+    int32_t fix = 0;
+    uint64_t run = nonstart;  // bit t: lanes t-d .. t are one group
+    for (uint32_t d = 1; run != 0; ++d) {
+        q_dn = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)q_dn, 0x130, 0xf, 0xf, true);  // wave_shl:1: lane i <- lane i + d
+        q_up = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)q_up, 0x138, 0xf, 0xf, true);  // wave_shr:1: lane i <- lane i - d
+        fix += q_dn < q ? (int32_t)(q_dn & 3u) : 0;
+        fix -= q_up > q ? (int32_t)(q_up & 3u) : 0;
+        run &= nonstart << d;
+    }
+    return fix;
+}
+#endif
 
 // Committed move application on the wave's LDS state (ListChange / ListSwap do_move).
 // OWN_LANE: the lane index is formed again here, behind an empty asm -- for a caller with no vector register to spare, whose compiler would otherwise
@@ -1313,7 +1371,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                     const uint64_t startmask = __ballot(have && (lane == 0 || !(key & NBR_SAME_FLAG)));
                     const bool more = havemask == ~0ULL && base + 64 < dim;
                     const uint32_t fo = 63u - (uint32_t)__clzll((unsigned long long)startmask);  // first lane of the last group
-                    if (more && fo == 0) {
+                    if (SF_SPEC_WIDE_TIES(more && fo == 0)) {
                         // one distance group wider than a chunk (degenerate ties): exact serial
                         // insertion top-k over the rest of the row.
                         TopK tk{~0ULL, 0u, ~0ULL};
@@ -1351,7 +1409,10 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                     if (Wc > 0) {
                         // sorted position = weight before me, corrected by the inversions inside my group
                         int32_t pos = (int32_t)(mbcnt64(w1) + 2u * mbcnt64(w2));
-                        const uint64_t nonstart = ~startmask & closedmask;  // lane continues the group of lane-1
+                        const uint64_t nonstart = SF_SPEC_TIES(~startmask & closedmask);  // lane continues the group of lane-1
+#ifdef SF_SPEC_TIE_KEY
+                        if (nonstart) pos += tie_key_fix(startmask, nonstart, it.ord, wc);
+#else
                         if (nonstart) {
                             const uint32_t packed = (it.ord << 2) | wc;
                             uint64_t run = nonstart;  // bit t: lanes t-d .. t are one group
@@ -1367,6 +1428,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                                 run &= nonstart << d;
                             }
                         }
+#endif
                         if (wc >= 1 && (uint32_t)pos < need) {
                             const uint32_t qi = (tl + emitted + (uint32_t)pos) & RCM;
                             rq[qi * 2] = mv0;
@@ -1417,8 +1479,10 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                     // LEAN: each half blanks the lanes past its row now (resolve() left the entries raw)
                     uint32_t l31 = lane & 31u;
                     if constexpr (LEAN) asm volatile("" : "+v"(l31));  // (formed per pass: hoisted out of the loops, `l31 < dim` is a 64-bit mask in spill lanes)
-                    const uint32_t key = LEAN ? row_key(half(C0.pk, C1.pk), l31) : (hi ? C1.pk : C0.pk);
-                    const bool have = key != NBR_END;
+                    // (SF_SPEC_ROWS_FULL: both halves lie inside their rows and every entry is finite -- `have` is a literal, and with it the blanking
+                    // selects, `havemask`, its halves and the count arm of `ncv` below)
+                    const uint32_t key = LEAN ? (SF_SPEC_ROW_HAVE(false) ? half(C0.pk, C1.pk) : row_key(half(C0.pk, C1.pk), l31)) : (hi ? C1.pk : C0.pk);
+                    const bool have = SF_SPEC_ROW_HAVE(key != NBR_END);
                     uint32_t nd = have ? (key & NBR_NODE_MASK) : 0u;  // unconditional read below (node 0 for the lanes past the row)
                     uint32_t slot_word = 0;
                     if constexpr (LEAN) {
@@ -1519,7 +1583,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                             it.pay1 = lane_change ? ic.pay1 : is.pay1;
                         }
                     }
-                    const uint64_t havemask = __ballot(have);
+                    const uint64_t havemask = SF_SPEC_ROW_HAVEMASK(__ballot(have));
                     // a group starts at the half's first lane and wherever the entry does not continue the previous one's distance.  LEAN: one compare,
                     // key < 0x8000 (no NBR_SAME_FLAG, not NBR_END) in general and key < NBR_END at the half's first lane
                     const uint64_t startmask = LEAN ? __ballot(key < NBR_END - min(l31, 1u) * (NBR_END - NBR_SAME_FLAG))
@@ -1553,7 +1617,11 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                         const uint32_t pa = __builtin_amdgcn_mbcnt_lo((uint32_t)w1, 0u) + 2u * __builtin_amdgcn_mbcnt_lo((uint32_t)w2, 0u);
                         const uint32_t pb = __builtin_amdgcn_mbcnt_hi((uint32_t)(w1 >> 32), 0u) + 2u * __builtin_amdgcn_mbcnt_hi((uint32_t)(w2 >> 32), 0u);
                         int32_t pos = (int32_t)(LEAN ? half(pa, pb) : (hi ? pb : pa));
-                        const uint64_t nonstart = ~startmask & closedmask;  // never crosses lane 32 (forced start)
+                        const uint64_t nonstart = SF_SPEC_TIES(~startmask & closedmask);  // never crosses lane 32 (forced start)
+#ifdef SF_SPEC_TIE_KEY
+                        static_assert(!std::is_same<RT, RouteTab>::value, "SF_SPEC_TIE_KEY: the (rank, position) ordinals");
+                        if (nonstart) pos += tie_key_fix(startmask, nonstart, it.ord, wc);
+#else
                         if (nonstart) {
                             const uint32_t packed = (it.ord << 2) | wc;
                             uint64_t run = nonstart;
@@ -1568,6 +1636,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                                 run &= nonstart << d;
                             }
                         }
+#endif
                         uint32_t* rq = ring + rq_off;
                         if (wc >= 1 && (uint32_t)pos < Kh) {
                             const uint32_t qi = (tl + (uint32_t)pos) & RCM;

@@ -6,8 +6,12 @@
 // hiprtc (loaded with dlopen: no link dependency, the library loads where hiprtc is absent) and keeps the module in a process-wide cache.
 // Any failure is remembered for its key and the launch goes through the ahead-of-time kernel.  The structs hold int32 fields only:
 // sf_debug_wave_spec / sf_debug_wave_spec_gate hand them to the tests as flat arrays in declaration order.
+// The key also carries three facts of the context's neighbour index (sf_nbr_facts.h) and the candidates that rest on them:
+// wave_spec_index_allowed -- pure, like wave_spec_wanted -- says which of them a key may compile in.
 #pragma once
 #include <dlfcn.h>
+
+#include "sf_nbr_facts.h"
 
 #include <fstream>
 #include <mutex>
@@ -21,22 +25,60 @@ struct WaveSpecKey {
     int32_t extras;
     int32_t capacity, cap_weight, dist_weight, depot, cap_level, dist_level;  // SF_WSPEC_X_MODEL: level_words' inputs
     int32_t la_size, limit, has_perm, has_explicit;                           // SF_WSPEC_X_LA / _LIMIT / _PERM / _EXPLICIT
+    // Facts of the context's neighbour index as three flags, and `index_x` = the SF_WSPEC_X_* bits compiled in that rest on them.
+    // These words come after the eighteen above, which keep their places and meanings: a caller that hands over eighteen words names a key
+    // of unknown facts and no such candidate.
+    int32_t wide_ties, ties, rows_full;  // some equal-distance group has 64 members or more; some group has two; every row has min(dim, 64) finite entries
+    int32_t index_x;
 };
+constexpr int32_t SF_WSPEC_KEY_WORDS_V1 = 18;  // the key before the index's facts: still taken and handed out by the sf_debug_wave_spec* entry points
 enum { SF_WSPEC_X_MODEL = 1, SF_WSPEC_X_LA = 2, SF_WSPEC_X_LIMIT = 4, SF_WSPEC_X_PERM = 8, SF_WSPEC_X_EXPLICIT = 16, SF_WSPEC_X_ALL = 31 };
+// The candidates that rest on the index's facts: the next bits of SF_AMD_WAVE_SPEC_EXTRAS, kept in the key's `index_x`.
+enum { SF_WSPEC_X_NO_WIDE = 32, SF_WSPEC_X_TIE_KEY = 64, SF_WSPEC_X_NO_TIES = 128, SF_WSPEC_X_ROWS_FULL = 256, SF_WSPEC_X_INDEX_ALL = 480 };
 // The candidates a launch compiles in unless SF_AMD_WAVE_SPEC_EXTRAS says otherwise: those that measured faster than the unit without them,
 // alone and on top of each other (profiles/wave_spec_ablation.txt).  The AcceptedCount limit lost 0.4 % alone and gained 0.2 % on
 // top of these three; the explicit seeds' absence lost 1.2 % alone and changed nothing on top: both stay arguments.
 constexpr int32_t SF_WSPEC_X_DEFAULT = SF_WSPEC_X_MODEL | SF_WSPEC_X_LA | SF_WSPEC_X_PERM;
+// Of the index's candidates (profiles/wave_index_facts_ablation.txt), on top of those three: no wide group +1.4 %, the packed tie
+// word +2.0 %, full rows +4.7 %, each above the unit without it in every round and each above the pairs it joins; together +7.8 %.  "No
+// ties" is never offered for the benchmark's index (it has ties) and so was never measured: it stays a switch.
+constexpr int32_t SF_WSPEC_X_INDEX_DEFAULT = SF_WSPEC_X_NO_WIDE | SF_WSPEC_X_TIE_KEY | SF_WSPEC_X_ROWS_FULL;
 static int32_t wave_spec_extras() {  // diagnostics (the ablation runs): read at every launch
     const char* e = std::getenv("SF_AMD_WAVE_SPEC_EXTRAS");
-    return e ? (std::atoi(e) & SF_WSPEC_X_ALL) : SF_WSPEC_X_DEFAULT;
+    return e ? (std::atoi(e) & (SF_WSPEC_X_ALL | SF_WSPEC_X_INDEX_ALL)) : (SF_WSPEC_X_DEFAULT | SF_WSPEC_X_INDEX_DEFAULT);
 }
-// The key of a launch: the instantiation, the model as the kernel sees it, the launch's parameters; `extras` = the candidates wanted (one whose
-// value does not fit a literal of its type is dropped).
+
+// What the candidates' gate reads: the constants the packed word's width follows from, and the facts as the key's flags.
+struct WaveSpecIndexGate {
+    int32_t V, dim, n_cap;
+    int32_t wide_ties, ties, rows_full;
+};
+static int32_t wave_spec_bits(uint32_t v) {  // bits that hold v (at least one)
+    int32_t b = 1;
+    while (v >> b) ++b;
+    return b;
+}
+static int32_t wave_spec_rb(int32_t V) { return wave_spec_bits((uint32_t)(V > 1 ? V - 1 : 0)); }
+static int32_t wave_spec_pb(int32_t n_cap) { return wave_spec_bits((uint32_t)(n_cap > 0 ? n_cap : 0)); }
+// Pure, beside wave_spec_wanted: the index candidates a key of these constants and facts may compile in.  One that its facts do not allow is
+// never offered -- the kernel would be wrong, not slow.
+static int32_t wave_spec_index_allowed(const WaveSpecIndexGate& g) {
+    int32_t a = 0;
+    if (!g.wide_ties) a |= SF_WSPEC_X_NO_WIDE;
+    if (wave_spec_rb(g.V) + wave_spec_pb(g.n_cap) <= 22) a |= SF_WSPEC_X_TIE_KEY;  // group (6 bits) | ordinal (RB + PB + 1) | weight (2) in one word
+    if (!g.ties) a |= SF_WSPEC_X_NO_TIES;
+    if (g.rows_full && g.dim >= 32) a |= SF_WSPEC_X_ROWS_FULL;  // (the paired pass reads the first 32 entries of two rows)
+    return a;
+}
+// The key of a launch: the instantiation, the model as the kernel sees it, the launch's parameters, the index's facts; `extras` = the
+// candidates wanted (one whose value does not fit a literal of its type, or whose facts do not hold, is dropped).
 template <class Model, class Params>
-static WaveSpecKey wave_spec_key(int32_t levels, int32_t wpe, const Model& m, const Params& q, int32_t extras) {
+static WaveSpecKey wave_spec_key(int32_t levels, int32_t wpe, const Model& m, const Params& q, const NbrFacts& nf, int32_t extras) {
     WaveSpecKey k{};
     k.levels = levels, k.wpe = wpe, k.V = m.V, k.dim = m.dim, k.n_cap = m.n_cap, k.k0 = q.leaf[0].max_nearby, k.k1 = q.leaf[1].max_nearby;
+    k.wide_ties = nf.tie_max >= 64, k.ties = nf.tie_max >= 2, k.rows_full = nf.rows_full != 0;
+    k.index_x = extras & SF_WSPEC_X_INDEX_ALL & wave_spec_index_allowed(WaveSpecIndexGate{k.V, k.dim, k.n_cap, k.wide_ties, k.ties, k.rows_full});
+    extras &= SF_WSPEC_X_ALL;
     auto fits = [](int64_t v) { return v >= INT32_MIN && v <= INT32_MAX; };
     if ((extras & SF_WSPEC_X_MODEL) && !(fits(m.capacity) && fits(m.cap_weight) && fits(m.dist_weight))) extras &= ~SF_WSPEC_X_MODEL;
     if ((m.perm != nullptr) != (m.inv != nullptr)) extras &= ~SF_WSPEC_X_PERM;  // (the two tables come and go together: one switch for both)
@@ -104,6 +146,11 @@ static std::vector<std::string> wave_spec_options(const WaveSpecKey& k, const st
     if (k.extras & SF_WSPEC_X_LIMIT) o.push_back(def("SF_SPEC_LIMIT", k.limit));
     if (k.extras & SF_WSPEC_X_PERM) o.push_back(def("SF_SPEC_HAS_PERM", k.has_perm));
     if (k.extras & SF_WSPEC_X_EXPLICIT) o.push_back(def("SF_SPEC_HAS_EXPLICIT", k.has_explicit));
+    if (k.index_x & SF_WSPEC_X_NO_WIDE) o.push_back(word("SF_SPEC_NO_WIDE", 1));
+    if (k.index_x & SF_WSPEC_X_TIE_KEY)
+        for (auto& x : {word("SF_SPEC_TIE_KEY", 1), word("SF_SPEC_RB", wave_spec_rb(k.V)), word("SF_SPEC_PB", wave_spec_pb(k.n_cap))}) o.push_back(x);
+    if (k.index_x & SF_WSPEC_X_NO_TIES) o.push_back(word("SF_SPEC_NO_TIES", 1));
+    if (k.index_x & SF_WSPEC_X_ROWS_FULL) o.push_back(word("SF_SPEC_ROWS_FULL", 1));
     return o;
 }
 static std::string wave_spec_kernel_expr(const WaveSpecKey& k) {
@@ -111,7 +158,9 @@ static std::string wave_spec_kernel_expr(const WaveSpecKey& k) {
 }
 static bool wave_spec_key_ok(const WaveSpecKey& k) {
     return (k.levels == 2 || k.levels == 4) && k.wpe >= 4 && k.wpe <= 6 && k.V >= 1 && k.dim >= 1 && k.n_cap >= 0 && k.k0 >= 1 && k.k1 >= 1 && (k.extras & ~SF_WSPEC_X_ALL) == 0 &&
-           (!(k.extras & SF_WSPEC_X_LA) || k.la_size >= 1) && (!(k.extras & SF_WSPEC_X_LIMIT) || k.limit >= 1);
+           (!(k.extras & SF_WSPEC_X_LA) || k.la_size >= 1) && (!(k.extras & SF_WSPEC_X_LIMIT) || k.limit >= 1) &&
+           (k.wide_ties | k.ties | k.rows_full | 1) == 1 && (!k.wide_ties || k.ties) &&
+           (k.index_x & ~wave_spec_index_allowed(WaveSpecIndexGate{k.V, k.dim, k.n_cap, k.wide_ties, k.ties, k.rows_full})) == 0;
 }
 
 // hiprtc through dlopen, by its versioned names.
