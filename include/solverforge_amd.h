@@ -884,6 +884,24 @@ typedef struct sf_tabu_record {
 } sf_tabu_record;
 int32_t sf_debug_tabu_script(sf_ctx* ctx, const sf_tabu_config* policy, int32_t levels, int32_t n_entity_ids, int32_t n_value_ids,
                              int32_t n_records, const sf_tabu_record* records, uint64_t* out_accept, uint64_t* out_state);
+/* The second local-search type of the reference's configuration (solverforge-config/src/phase.rs:148-155): Variable Neighborhood Descent
+ * (phase/localsearch/vnd/phase.rs:31-404).  The neighbourhoods are the context's declared leaves in declaration order (the order of the
+ * sf_selector_add* calls), one leaf each, compiled with SelectionOrder::Original.  A step pulls the whole cursor of neighbourhood k and
+ * applies the first strictly best candidate that beats the current score strictly, then k = 0; a step that finds none applies nothing,
+ * still counts as a step (step index and seed draw advance) and sets k += 1.  A replica is done at k == n: it runs no further step, in
+ * this launch or a later one, until the next sf_phase_start.  sf_stats::moves_accepted and moves_applied count the applied pick only.
+ * While it holds, the acceptor, forager, random_ties, selection_order and sf_union_configure settings are ignored; sf_solver_configure or
+ * sf_solver_configure_default returns the context to acceptor-forager search.  It takes effect at the next sf_phase_start: a launch
+ * under it in a phase that was not started under it is SF_ERR_INVALID.  Launches (sf_solve_steps, sf_solve_moves, sf_solve_step_traced:
+ * flag bit 1 = strictly better than the current score, bit 2 on the pick; a replica that is done returns no candidate) run in the
+ * generic engine whatever the model.  SF_ERR_UNSUPPORTED at launch: a list ruin leaf, a list precedence leaf, a forced block or wave
+ * engine, more leaves than a union holds; sf_step_decide* and sf_portfolio_migrate_local while it holds. */
+int32_t sf_solver_configure_vnd(sf_ctx* ctx);
+/* State of one replica (after sf_phase_start under it, else SF_ERR_INVALID): the neighbourhood of its next step, the number of
+ * neighbourhoods, whether it is done (k == n), and how many of its steps found nothing. */
+int32_t sf_get_vnd_state(sf_ctx* ctx, int32_t replica, int32_t* out_k, int32_t* out_n, int32_t* out_done, uint64_t* out_idle_steps);
+/* How many replicas are done: one read of 8 bytes per replica. */
+int32_t sf_vnd_done_count(sf_ctx* ctx, int32_t* out);
 int32_t sf_solver_set_engine(sf_ctx* ctx, int32_t engine); /* sf_engine_kind; SF_ERR_UNSUPPORTED if it cannot run this model */
 int32_t sf_solver_get_engine(sf_ctx* ctx, int32_t* out_engine); /* the engine launches resolve to (after sf_initialize) */
 /* How the wave engine laid out its last fused launch (diagnostics; tests assert the path they mean to cover was taken):

@@ -98,6 +98,7 @@ SYMBOLS = [
     "sf_get_annealing_state", "sf_debug_anneal_chunks", "sf_solver_set_step_seeds",
     "sf_solver_configure_great_deluge", "sf_solver_configure_step_counting", "sf_get_acceptor_state", "sf_debug_acceptor_script",
     "sf_solver_configure_tabu", "sf_get_tabu_state", "sf_debug_tabu_script",
+    "sf_solver_configure_vnd", "sf_get_vnd_state", "sf_vnd_done_count",
     "sf_solver_set_engine", "sf_solver_get_engine", "sf_list_wave_layout", "sf_list_arith_flags", "sf_constraint_add_pair_join", "sf_constraint_add_uni_program", "sf_provider_declare", "sf_phase_start", "sf_solve_steps", "sf_solve_moves", "sf_solve_step_traced", "sf_get_stats", "sf_get_stats_sum", "sf_get_best_scores",
     "sf_profile_solve", "sf_download_scalar", "sf_download_list", "sf_portfolio_unique_id",
     "sf_portfolio_init", "sf_portfolio_allgather_best", "sf_portfolio_broadcast_best", "sf_portfolio_destroy", "sf_portfolio_migrate_local",
@@ -181,6 +182,9 @@ def load():
     L.sf_solver_configure_tabu.argtypes = [vp, C.POINTER(TabuConfigStruct)]
     L.sf_get_tabu_state.argtypes = [vp, i32, vp, vp, i64, vp, C.POINTER(i64), i64, vp, C.POINTER(i64), vp, C.POINTER(i32), vp, C.POINTER(i32)]
     L.sf_debug_tabu_script.argtypes = [vp, C.POINTER(TabuConfigStruct), i32, i32, i32, i32, vp, vp, vp]
+    L.sf_solver_configure_vnd.argtypes = [vp]
+    L.sf_get_vnd_state.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(u64)]
+    L.sf_vnd_done_count.argtypes = [vp, C.POINTER(i32)]
     L.sf_solver_set_engine.argtypes = [vp, i32]
     L.sf_solver_get_engine.argtypes = [vp, C.POINTER(i32)]
     L.sf_list_wave_layout.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]

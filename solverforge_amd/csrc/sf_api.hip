@@ -158,6 +158,8 @@ struct sf_ctx {
     bool tabu_configured = false;  // sf_solver_configure_tabu was called: acceptor kind 7 is taken only then (sf_solver_configure)
     uint64_t* d_tabu_arena = nullptr;  // [R][arena words of the policy and the model] stamp tables and rings (sf_tabu.h), sized at sf_phase_start
     uint64_t tabu_arena_cap = 0;
+    bool vnd = false;   // sf_solver_configure_vnd: the local-search type is Variable Neighborhood Descent until the next sf_solver_configure
+    int vnd_n = -1;     // neighbourhoods of the phase that was started under it (sf_api_vnd.inc)
     uint64_t* d_explicit = nullptr;
     int64_t n_explicit = 0;
     // trace buffers
@@ -1189,6 +1191,9 @@ static int ensure_trace(sf_ctx* ctx, int64_t cap) {
     return SF_OK;
 }
 
+// what SearchParams::acceptor carries for the configured local-search type: the acceptor kind, or VND_KIND (no acceptor)
+static int search_kind(const sf_ctx* ctx) { return ctx->vnd ? (int)VND_KIND : ctx->cfg.acceptor; }
+
 static void fill_search_params(sf_ctx* ctx, SearchParams& p) {
     p.acceptor = ctx->cfg.acceptor;
     p.dla_tolerance = ctx->dla_tolerance;
@@ -1198,6 +1203,13 @@ static void fill_search_params(sf_ctx* ctx, SearchParams& p) {
     if (ctx->cfg.forager == SF_FORAGER_FIRST_LAST_STEP_SCORE_IMPROVING && ctx->cfg.accepted_count_limit <= 0) p.limit = 0;
     p.random_ties = ctx->cfg.random_ties;
     p.order = ctx->cfg.selection_order;
+    if (ctx->vnd) {  // Variable Neighborhood Descent: a whole cursor in SelectionOrder::Original, the first strictly best candidate stays (sf_step.h)
+        p.acceptor = VND_KIND;
+        p.forager = SF_FORAGER_BEST_SCORE;
+        p.limit = 1;
+        p.random_ties = 0;
+        p.order = SF_ORDER_ORIGINAL;
+    }
     p.random_seed = ctx->cfg.random_seed;
     p.dry_run = 0;
     {  // diagnostics only (A/B measurements of the generic engine's trial evaluators)
@@ -1527,6 +1539,7 @@ int32_t sf_solver_configure(sf_ctx* ctx, const sf_solver_config* cfg) {
     if ((cfg->acceptor == SF_ACCEPT_LATE_ACCEPTANCE || cfg->acceptor == SF_ACCEPT_DIVERSIFIED_LATE_ACCEPTANCE) && cfg->late_acceptance_size <= 0)
         return fail(ctx, SF_ERR_INVALID, "late_acceptance_size must be > 0");  // both acceptors assert it (late_acceptance.rs:71, diversified_late_acceptance.rs:87-90)
     ctx->cfg = *cfg;
+    ctx->vnd = false;  // an acceptor and a forager were named: acceptor-forager local search again (sf_solver_configure_vnd)
     if (ctx->search_alloc) ctx->sp.la_size = cfg->late_acceptance_size > 0 ? cfg->late_acceptance_size : 1;
     return SF_OK;
 }
@@ -1675,6 +1688,8 @@ static void anneal_init_state(const sf_annealing_config& a, int levels, uint64_t
 
 static int tabu_phase_rows(sf_ctx* ctx, std::vector<uint64_t>& st);  // sf_api_tabu.inc
 static const char* tabu_launch_refusal(sf_ctx* ctx);
+static void vnd_phase_rows(sf_ctx* ctx, std::vector<uint64_t>& st);  // sf_api_vnd.inc
+static const char* vnd_launch_refusal(sf_ctx* ctx);
 
 // phase_started for every replica; replica r is seeded with seed + r
 static int anneal_phase_start(sf_ctx* ctx) {
@@ -1686,7 +1701,8 @@ static int anneal_phase_start(sf_ctx* ctx) {
     for (int r = 0; r < ctx->R; ++r) anneal_init_state(a, ctx->levels, seed + (uint64_t)r, st.data() + (size_t)r * SA_WORDS);
     // GreatDeluge / StepCountingHillClimbing keep their state at the head of the same rows (sf_step.h): zeros and the acceptor's parameter;
     // the phase-start kernels fill in the rest from the initial score (acceptor_phase_started)
-    const int acceptor = ctx->cfg.acceptor;
+    const int acceptor = search_kind(ctx);
+    if (acceptor == VND_KIND) vnd_phase_rows(ctx, st);  // Variable Neighborhood Descent: the number of neighbourhoods in the same rows (sf_step.h VND_*)
     if (acceptor == SF_ACCEPT_GREAT_DELUGE || acceptor == SF_ACCEPT_STEP_COUNTING_HILL_CLIMBING)
         for (int r = 0; r < ctx->R; ++r) {
             uint64_t* w = st.data() + (size_t)r * SA_WORDS;
@@ -1796,7 +1812,7 @@ int32_t sf_phase_start(sf_ctx* ctx) {
     HIPCHK(ctx, hipMemsetAsync(ctx->sp.seed_draws, 0, (size_t)ctx->R * 8, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->sp.stats, 0, (size_t)ctx->R * SF_STATS_WORDS * 8, ctx->stream));
     if ((rc = anneal_phase_start(ctx))) return rc;
-    ctx->sp.acceptor = ctx->cfg.acceptor;  // the phase-start kernels run acceptor.phase_started of GreatDeluge / StepCountingHillClimbing
+    ctx->sp.acceptor = search_kind(ctx);  // the phase-start kernels run acceptor.phase_started of GreatDeluge / StepCountingHillClimbing, and vnd_phase_started
     if ((rc = ruin_phase_start(ctx))) return rc;
     if (ctx->has_list_model)
         hipLaunchKernelGGL(k_list_phase_start, dim3(ctx->R), dim3(256), 0, ctx->stream, ctx->lm, ctx->sp);
@@ -1902,8 +1918,11 @@ static int launch_mixed(sf_ctx* ctx, SearchParams& p, int grid, bool trace) {
     // (runtime/compiler/default_local_search/policy.rs:104-108).  A configured root union (sf_union_configure) keeps the
     // order of the sf_selector_add calls instead: its weights and the Sequential / RoundRobin child order follow the
     // declaration order of the UnionMoveSelectorConfig's children (vec_union.rs:119-124).
+    // Variable Neighborhood Descent: the neighbourhoods are the declared leaves in declaration order, one leaf each; the union's own
+    // settings are ignored (one child is live per step: sf_mixed_wave.hip)
+    const bool vnd = p.acceptor == VND_KIND;
     std::vector<const SelectorSpec*> ordered;
-    if (union_is_custom(ctx)) {
+    if (union_is_custom(ctx) || vnd) {
         for (auto& s : ctx->selectors) ordered.push_back(&s);
     } else {
         for (int kind : {SF_SEL_LIST_PRECEDENCE, SF_SEL_LIST_PERMUTE,  // the precedence pair leads the list policy (policy/list.rs:24-33)
@@ -1988,10 +2007,11 @@ static int launch_mixed(sf_ctx* ctx, SearchParams& p, int grid, bool trace) {
     }
     const GenericKnobs knobs = generic_knobs();
     gl.plf.slow = knobs.plf_slow, gl.plf.force64 = knobs.plf_force64;
-    gl.union_order = ctx->union_order >= 0 ? ctx->union_order : (gl.n > 1 ? SF_UNION_STRATIFIED_RANDOM : SF_UNION_SEQUENTIAL);
-    gl.union_custom = union_is_custom(ctx) && gl.n > 1 ? 1 : 0;
+    if (vnd && gl.n != ctx->vnd_n) return fail(ctx, SF_ERR_INVALID, "variable neighborhood descent: the leaves changed since sf_phase_start");
+    gl.union_order = vnd ? SF_UNION_SEQUENTIAL : ctx->union_order >= 0 ? ctx->union_order : (gl.n > 1 ? SF_UNION_STRATIFIED_RANDOM : SF_UNION_SEQUENTIAL);
+    gl.union_custom = !vnd && union_is_custom(ctx) && gl.n > 1 ? 1 : 0;
     for (int l = 0; l < GL; ++l) gl.weight[l] = 1;
-    if (!ctx->union_weights.empty()) {
+    if (!vnd && !ctx->union_weights.empty()) {
         if ((int)ctx->union_weights.size() != gl.n) return fail(ctx, SF_ERR_INVALID, "union weight count must match child count");
         for (int l = 0; l < gl.n; ++l) gl.weight[l] = ctx->union_weights[l];
     }
@@ -2048,6 +2068,13 @@ static int launch_search(sf_ctx* ctx, SearchParams& p, int grid, bool trace) {
         if (ctx->sp.acceptor != SF_ACCEPT_TABU_SEARCH) return fail(ctx, SF_ERR_INVALID, "tabu search: sf_phase_start after the acceptor was configured");
         if (const char* why = tabu_launch_refusal(ctx)) return fail(ctx, SF_ERR_UNSUPPORTED, why);
         trace = true;
+    }
+    // Variable Neighborhood Descent (sf_step.h): the generic engine's TRACE instantiations whatever the model -- scalar-only, list-only or
+    // mixed.  Its rows carry k and n: a phase that was not started under it has neither
+    if (p.acceptor == VND_KIND) {
+        if (ctx->sp.acceptor != VND_KIND) return fail(ctx, SF_ERR_INVALID, "variable neighborhood descent: sf_phase_start after sf_solver_configure_vnd");
+        if (const char* why = vnd_launch_refusal(ctx)) return fail(ctx, SF_ERR_UNSUPPORTED, why);
+        return launch_mixed(ctx, p, grid, true);
     }
     // the 2-leaf nearby union has its own engines; every other union runs in the generic N-leaf engine
     // a configured root union (order / weights other than the default policy's) runs in the generic engine too
@@ -2244,6 +2271,8 @@ int32_t sf_portfolio_migrate_local(sf_ctx* ctx, int32_t n_elite, int32_t n_repla
     if (!ctx->search_alloc) return fail(ctx, SF_ERR_INVALID, "sf_phase_start first");
     if (!ctx->has_list_model || ctx->has_scalar_model)
         return fail(ctx, SF_ERR_UNSUPPORTED, "elite migration: list-only models (the adopted state is the list class's best solution)");
+    if (ctx->vnd)  // a descent keeps k and its current score per replica: an adopted solution has no place in them
+        return fail(ctx, SF_ERR_UNSUPPORTED, "elite migration: not under variable neighborhood descent");
     if (ctx->cfg.acceptor != SF_ACCEPT_HILL_CLIMBING && ctx->cfg.acceptor != SF_ACCEPT_LATE_ACCEPTANCE &&
         ctx->cfg.acceptor != SF_ACCEPT_DIVERSIFIED_LATE_ACCEPTANCE)  // every acceptor not listed is refused: an adopted solution has no place in its schedule
         return fail(ctx, SF_ERR_UNSUPPORTED, "elite migration: HillClimbing / LateAcceptance / DiversifiedLateAcceptance (an annealing replica keeps a temperature schedule, a great deluge its water level, a step count its best step score, a tabu search its memories)");
@@ -2458,3 +2487,4 @@ extern "C" int32_t sf_debug_phases(uint64_t* out8) {  // diagnostic builds only 
 #include "sf_api_anneal_debug.inc"
 #include "sf_api_acceptor_debug.inc"
 #include "sf_api_tabu.inc"
+#include "sf_api_vnd.inc"

@@ -216,6 +216,8 @@ static int32_t step_decide_impl(sf_ctx* ctx, int32_t replica, const sf_move_t* e
         return fail(ctx, SF_ERR_INVALID, "bad sf_step_decide arguments");
     if (!ctx->has_scalar_model || ctx->has_list_model) return fail(ctx, SF_ERR_UNSUPPORTED, "sf_step_decide: scalar-only models (ScalarCandidate edits)");
     if (int rc = compound_model_gates(ctx)) return rc;
+    if (ctx->vnd)
+        return fail(ctx, SF_ERR_UNSUPPORTED, "sf_step_decide: not under variable neighborhood descent (the provider step runs an acceptor and a forager)");
     if (ctx->cfg.acceptor == SF_ACCEPT_TABU_SEARCH)
         return fail(ctx, SF_ERR_UNSUPPORTED, "sf_step_decide: not under TabuSearch (a compound candidate has no fixed-size move signature)");
     if (ctx->cfg.acceptor == SF_ACCEPT_SIMULATED_ANNEALING)

@@ -79,7 +79,8 @@ struct SearchParams {
     int32_t n_leaves;
     LeafSpec leaf[MAX_LEAVES];
     int32_t acceptor;     // 0 HC, 1 LA, 2 never (dry run), 3 simulated annealing (state in `sa`), 4 diversified late acceptance,
-                          // 5 great deluge, 6 step counting hill climbing (state in sa.state: sf_step.h AX_*), 7 tabu search (sf_tabu.h TB_*)
+                          // 5 great deluge, 6 step counting hill climbing (state in sa.state: sf_step.h AX_*), 7 tabu search (sf_tabu.h TB_*),
+                          // 8 no acceptor: the Variable Neighborhood Descent phase (sf_step.h VND_*; the generic engine only)
     int32_t la_size;
     int32_t forager;      // sf_forager_kind: 0 accepted count, 1 first accepted, 2 best score, 3 / 4 improving (sf_forager.h)
     int32_t limit;        // accepted-count limit (forager 4: 0 = none)

@@ -1024,6 +1024,17 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
     const uint64_t cm_hi = use_cm ? __ballot(lane + 64 < (uint32_t)V && gcd_u32(lane + 64, (uint32_t)V) == 1) : 0ull;
 
     for (int64_t step = 0; step < p.n_steps; ++step) {
+        // Variable Neighborhood Descent (the TRACE instantiations carry it; sf_step.h): the neighbourhood of this step.  A replica whose phase
+        // has ended runs no step: it leaves the loop as a spent move budget does, with its step index, seed draws, counters and state as
+        // they are.  That is safe for the waves that share its workgroup: no barrier follows, and the one LDS region they share (the static
+        // precedence graph) was written alike by every wave before the loop.
+        [[maybe_unused]] uint32_t vnd_k = 0;
+        if constexpr (TRACE)
+            if (acceptor == VND_KIND) {
+                bool vnd_done;
+                vnd_step_begin(p.sa.state + (size_t)r * SA_WORDS, vnd_k, vnd_done);
+                if (vnd_done) break;
+            }
         // load-balance / balance aggregates of the step snapshot (the tables change only at commit): every lane gets the totals
         int64_t lbv[4] = {0, 0, 0, 0};
         if (tables && sm.grp_level >= 0 && sm.grp_mode >= 1) {
@@ -1342,6 +1353,18 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
             }
             if (u_ord == 2) u_cur = u_off;  // RotatingRoundRobin starts at the seeded offset
         }
+        // Variable Neighborhood Descent opens the cursor of neighbourhood k alone (phase.rs:79-80): every other leaf is an exhausted child
+        // from the start, as a zero-weight one is.  The host hands over unit weights and no custom union, so the one live child weighs 1.
+        if constexpr (TRACE)
+            if (acceptor == VND_KIND) {
+#pragma unroll
+                for (int l = 0; l < GL; ++l) {
+                    if (l >= nl || (uint32_t)l == vnd_k) continue;
+                    exmask |= 1u << l;
+                    lt.set(l, LeafTab::EX, 1);
+                }
+                live_weight = 1;
+            }
         uint64_t u_order = 0;  // rotated child order of this step, 4 bits per position (nl <= 16)
         for (uint32_t pos = 0; pos < (uint32_t)nl; ++pos) u_order |= (uint64_t)((u_off + pos * u_str) % (uint32_t)nl) << (4u * pos);
         u_order = uni64(u_order);
@@ -2577,6 +2600,8 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                         if (consult) tabu_sig_generic(my_kind, m0, m1, s_vals, s_visits, s_off, tabu_scalar_scope, tabu_list_scope, sig);
                         acc = tabu_accepts<L>(tabu, consult, sc, sig);
                     }
+                if constexpr (TRACE)  // Variable Neighborhood Descent: no acceptor, a possible pick beats the current score strictly
+                    if (acceptor == VND_KIND) acc = vnd_accepts<L>(consult, sc, curv);
                 SaChunk sach;
                 if (annealing) acc = sa_decide<L>(saw, p.sa, consult, sc, curv, lane, sach);
                 uint64_t accmask = __ballot(acc);
@@ -2645,7 +2670,9 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                 const uint32_t nacc = (uint32_t)__popcll(accmask);
                 accepted += nacc;
                 st_gen += nconsumed;
-                st_acc += nacc;
+                [[maybe_unused]] bool count_accepts = true;  // Variable Neighborhood Descent counts the applied pick only, at the commit (phase.rs:117-127)
+                if constexpr (TRACE) count_accepts = acceptor != VND_KIND;
+                st_acc += count_accepts ? nacc : 0u;
                 st_scored += nvalid;
                 st_calc += (uint32_t)__popcll(__ballot(consumed && doable));
                 if (tracing && consumed) {
@@ -2865,6 +2892,8 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
 #pragma unroll
             for (int kk = 0; kk < L; ++kk) cur[kk] = best.v[kk];
             st_applied += 1;
+            if constexpr (TRACE)
+                if (acceptor == VND_KIND) st_acc += 1;  // record_move_accepted + record_move_applied of the found step
         } else if (tracing && lane == 0) {
             p.trace_applied[0] = 0;
         }
@@ -2904,6 +2933,8 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                 if (acceptor == 5 || acceptor == 6) ax_step_ended<L>(acceptor, lane == 0, cur, p.sa.state + (size_t)r * SA_WORDS);
             if constexpr (TRACE)
                 if (acceptor == 7) tabu_step_ended<L>(p.sa.state + (size_t)r * SA_WORDS, lane == 0, cur, applied ? &pick_sig : nullptr);
+            if constexpr (TRACE)
+                if (acceptor == VND_KIND) vnd_step_ended(p.sa.state + (size_t)r * SA_WORDS, lane == 0, applied);
             if (annealing) sa_step_ended(saw, p.sa, lane);
             wave_sync();
             st_steps += 1;

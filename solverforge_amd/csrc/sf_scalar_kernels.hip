@@ -1418,6 +1418,7 @@ __global__ __launch_bounds__(256) void k_scalar_phase_start(ScalarModel m, Searc
         p.step_index[r] = 0;
         p.has_best[r] = 1;
         acceptor_phase_started(p.acceptor, cur, p.sa.state + (size_t)r * SA_WORDS);  // GreatDeluge / StepCountingHillClimbing
+        vnd_phase_started(p.acceptor, p.sa.state + (size_t)r * SA_WORDS);  // Variable Neighborhood Descent: k = 0, nothing found yet
     }
     if (p.acceptor == 7) tabu_phase_started(p.sa.state + (size_t)r * SA_WORDS, cur, threadIdx.x, blockDim.x);  // TabuSearch: best, counters, the arena
 }

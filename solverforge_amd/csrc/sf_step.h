@@ -13,6 +13,9 @@
 //    ax_step_begin, ax_accepts, ax_step_ended.  Defined here alone and called from all five places.  In the four fused engines the calls
 //    are compiled into the TRACE instantiations only, and a launch under these two acceptors takes those: the untraced
 //    kernels, which every other policy runs, hold none of this code.
+// 3. The Variable Neighborhood Descent phase (phase/localsearch/vnd/phase.rs:31-167 solve_vnd_with_resources, :181-404
+//    find_best_improving_move; neighbourhoods compiled with SelectionOrder::Original, runtime/compiler/local_search.rs:55-89):
+//    vnd_phase_started, vnd_step_begin, vnd_accepts, vnd_step_ended.  Called by the generic engine's TRACE instantiations.
 //
 // Nothing here owns memory: the callers keep their registers and LDS words and pass references or row pointers.  SimulatedAnnealing
 // (sa_decide / sa_commit / sa_step_ended) and the statistics counters stay with the kernels.
@@ -31,6 +34,15 @@ namespace sf {
 //   AX_PARAM  1  from the host at phase start: rain_speed (f64 bits) / step_count_limit
 enum : int { AX_LEVEL = 0, AX_INCR = 4, AX_SINCE = 8, AX_PARAM = 9, AX_WORDS = 10 };
 static_assert(AX_WORDS <= SA_WORDS, "acceptors 5 and 6 live in the replica's acceptor-state row");
+// State of the Variable Neighborhood Descent phase (group 3 below), in the same words: no acceptor runs under it.
+//   VND_K     the neighbourhood of the next step, 0 .. n
+//   VND_N     the number of neighbourhoods, from the host at phase start
+//   VND_DONE  k == n: the replica runs no further step (it survives launch boundaries; a new phase start clears it)
+//   VND_IDLE  steps that found nothing
+enum : int { VND_K = 0, VND_N = 1, VND_DONE = 2, VND_IDLE = 3, VND_WORDS = 4 };
+// The phase travels through SearchParams::acceptor as this kind.  It is no acceptor of the C ABI (sf_solver_configure refuses it): only
+// sf_solver_configure_vnd sets it.
+enum : int { VND_KIND = 8 };
 }  // namespace sf
 
 #if defined(__HIPCC__)
@@ -255,6 +267,35 @@ __device__ __forceinline__ void ax_step_ended(int acceptor, bool writer, const i
             ax_row[AX_SINCE] += 1;
         }
     }
+}
+
+// ---- Variable Neighborhood Descent -------------------------------------------------------------------------------------------------
+// k = 0 at phase start (phase.rs:48); the host wrote n.  A phase without a neighbourhood is done before its first step (`while k < n`).
+__device__ __forceinline__ void vnd_phase_started(int acceptor, uint64_t* vnd_row) {
+    if (acceptor != VND_KIND) return;
+    vnd_row[VND_K] = 0;
+    vnd_row[VND_DONE] = vnd_row[VND_N] == 0 ? 1 : 0;
+    vnd_row[VND_IDLE] = 0;
+}
+// The neighbourhood of this step and whether the phase has ended for the replica, wave-uniform (phase.rs:58: `while k < n`)
+__device__ __forceinline__ void vnd_step_begin(const uint64_t* vnd_row, uint32_t& k, bool& done) {
+    k = uni((uint32_t)vnd_row[VND_K]);
+    done = uni((uint32_t)vnd_row[VND_DONE]) != 0;
+}
+// A candidate that reaches the comparison (`consult`: doable and not held back by a requires_*_improvement gate, phase.rs:279-333) is a
+// possible pick when it beats the current score strictly (:339).  Among those the step keeps the first strictly best one (:340-357): the
+// BestScore pick without random ties.
+template <int L>
+__device__ __forceinline__ bool vnd_accepts(bool consult, const ScoreV<L>& sc, const ScoreV<L>& cur) {
+    return consult && score_cmp<L>(sc, cur) > 0;
+}
+// Found: k = 0 (phase.rs:132).  Not found: k += 1 (:136), and the step counts among the idle ones.  By the one lane `writer`.
+__device__ __forceinline__ void vnd_step_ended(uint64_t* vnd_row, bool writer, bool applied) {
+    if (!writer) return;
+    const uint64_t k = applied ? 0 : vnd_row[VND_K] + 1;
+    vnd_row[VND_K] = k;
+    vnd_row[VND_DONE] = k >= vnd_row[VND_N] ? 1 : 0;
+    if (!applied) vnd_row[VND_IDLE] += 1;
 }
 
 }  // namespace sf

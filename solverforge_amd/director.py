@@ -675,6 +675,39 @@ class GpuScoreDirector:
         check(self._L.sf_debug_tabu_script(self._h, C.byref(cfg), levels, n_entity_ids, n_value_ids, n, ptr(records), ptr(accept), ptr(state)), self._h)
         return accept[:n], state[:n]
 
+    def configure_vnd(self):
+        """Local-search type Variable Neighborhood Descent (vnd/phase.rs:31-404): the neighbourhoods are the declared selectors in
+        declaration order, one leaf each, in SelectionOrder.ORIGINAL.  Takes effect at the next phase_start; acceptor, forager, random
+        ties, selection order and the union's settings are ignored until configure() / configure_default() names them again.  A step
+        applies the first strictly best strictly improving move of neighbourhood k (then k = 0) or nothing (k += 1); a replica is done at
+        k == n.  Runs in the generic engine whatever the model; ruin and precedence leaves and forced engines are refused at launch."""
+        check(self._L.sf_solver_configure_vnd(self._h), self._h)
+
+    def vnd_state(self, replica=0):
+        """{"k": neighbourhood of the next step, "n": neighbourhoods, "done": k == n, "idle_steps": steps that found nothing} of one replica."""
+        k, n, done, idle = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_uint64(0)
+        check(self._L.sf_get_vnd_state(self._h, replica, C.byref(k), C.byref(n), C.byref(done), C.byref(idle)), self._h)
+        return {"k": k.value, "n": n.value, "done": bool(done.value), "idle_steps": int(idle.value)}
+
+    def vnd_done_count(self):
+        """How many replicas have ended their descent (k == n)."""
+        n = C.c_int32(0)
+        check(self._L.sf_vnd_done_count(self._h, C.byref(n)), self._h)
+        return n.value
+
+    def solve_vnd(self, max_steps, steps_per_launch=64):
+        """Descend every replica to a local optimum of all neighbourhoods: launches of steps_per_launch steps until every replica is done
+        or max_steps steps per replica were asked for.  Returns the number of replicas that are done.  (A done replica costs a launch
+        nothing: it runs no step.)"""
+        asked = 0
+        done = self.vnd_done_count()
+        while done < self.n_replicas and asked < max_steps:
+            n = min(int(steps_per_launch), max_steps - asked)
+            self.solve_steps(n)
+            asked += n
+            done = self.vnd_done_count()
+        return done
+
     def annealing_state(self, replica=0):
         """(current temperatures per score level, still calibrating?) of one replica's acceptor."""
         t = np.zeros(4, dtype=np.float64)
