@@ -13,7 +13,7 @@ d = sfa.build_cvrp(p, n_replicas=R)
 d.configure(sfa.SolverConfig(random_seed=0))
 d.calculate_score(); d.phase_start()
 L = _lib.load()
-out = np.zeros(8, dtype=np.uint64)
+out = np.zeros(10, dtype=np.uint64)  # (a library from before the lockstep round fills eight)
 for it in range(3):
     d.solve_steps(200)
 L.sf_debug_phases_wave_2(out.ctypes.data_as(ctypes.c_void_p))
@@ -23,7 +23,8 @@ for it in range(n):
 L.sf_debug_phases_wave_2(out.ctypes.data_as(ctypes.c_void_p))
 a = d.total_stats()
 src = a["sources_scanned"] - b["sources_scanned"]
-names = ["paired_passes", "single_leaf0", "single_leaf1", "rest_calls_pair_leaf0", "rest_calls_pair_leaf1", "rest_iters_leaf0", "rest_iters_leaf1", "rest_iters_empty"]
+names = ["paired_passes", "single_leaf0", "single_leaf1", "rest_calls_pair_leaf0", "rest_calls_pair_leaf1", "rest_iters_leaf0", "rest_iters_leaf1", "rest_iters_empty",
+         "lockstep_passes", "lockstep_exits"]  # (the round's passes count in paired_passes too; an exit hands the rest of a step to the general loop)
 o = {k: int(v) for k, v in zip(names, out)}
 o["sources"] = int(src); o["steps"] = int(a["step_count"] - b["step_count"]); o["moves"] = int(a["moves_evaluated"] - b["moves_evaluated"])
 o["per_source"] = {k: round(int(v) / max(src, 1), 4) for k, v in zip(names, out)}

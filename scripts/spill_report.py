@@ -6,7 +6,9 @@ usage: spill_report.py [file.s] kernel-substring [kernel-substring ...]
 
 Without a .s the L = 2 wave unit is compiled with -DSF_ISA_MARK into a temporary directory.  A region x is what control flow reaches
 between the marks x_begin and x_end (the compiler moves blocks around, so the regions are followed through the branches, not read off
-the text); resolve()'s slow path is inlined several times and is one row.
+the text); resolve()'s slow path is inlined several times and is one row.  The kernels with the lockstep round have two more
+regions, sym_fill and sym_replay -- the round's fill loop and its batch; the round's copy of the paired pass lies inside sym_fill and counts in
+`pair` (and `pair_rest`, `resolve_slow`) as well, so those rows hold two copies there: sym_fill less one copy of `pair` is the round's fill glue.
   spill VGPR   a VGPR that appears only as the destination of v_writelane or the source of v_readlane
   step loop    the backward branch with the largest span
   const/carried  a reload of a slot (register, lane) written only before the step loop / written inside it

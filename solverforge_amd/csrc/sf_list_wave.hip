@@ -624,8 +624,19 @@ __device__ __forceinline__ uint32_t nearby_source_to_ring(const ListModel& m, co
     return emitted;
 }
 
+// SF_WAVE_SYM: the lockstep round of the RBATCH kernels.  -DSF_WAVE_SYM=0 compiles the loop without it; the run-time unit takes the
+// same define from the environment switch SF_AMD_NO_WAVE_SYM, read once per process (sf_wave_spec.h).
+#ifndef SF_WAVE_SYM
+#define SF_WAVE_SYM 1
+#endif
+
 #if defined(SF_PHASE_PROFILE) || defined(SF_GEN_COUNT)
-__device__ unsigned long long g_phase[8];
+#ifdef SF_GEN_COUNT
+#define SF_PHASE_WORDS 10
+#else
+#define SF_PHASE_WORDS 8
+#endif
+__device__ unsigned long long g_phase[SF_PHASE_WORDS];
 #endif
 // analysis builds (-DSF_ISA_MARK): comments in the generated assembly that delimit the hot regions, for static instruction counts per region
 #ifdef SF_ISA_MARK
@@ -644,12 +655,13 @@ __device__ unsigned long long g_phase[8];
 #define PH_DUMP \
     if (lane == 0) for (int _k = 0; _k < 8; ++_k) atomicAdd(&g_phase[_k], (unsigned long long)ph_acc[_k]);
 #elif defined(SF_GEN_COUNT)  // event counts of the generation instead of clocks (scripts/gen_count.py): 0 paired passes, 1 / 2 single-source passes of leaf 0 / 1,
-// 3 / 4 gen_rest calls out of a paired pass for leaf 0 / 1, 5 / 6 gen_rest chunk iterations of leaf 0 / 1, 7 iterations that found no key
-#define PH_DECL uint64_t ph_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+// 3 / 4 gen_rest calls out of a paired pass for leaf 0 / 1, 5 / 6 gen_rest chunk iterations of leaf 0 / 1, 7 iterations that found no key,
+// 8 paired passes of the lockstep round (they count in 0 too), 9 exits from the round into the general loop
+#define PH_DECL uint64_t ph_acc[SF_PHASE_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #define PH(i)
 #define GC(i) ph_acc[i] += 1;
 #define PH_DUMP \
-    if (lane == 0) for (int _k = 0; _k < 8; ++_k) atomicAdd(&g_phase[_k], (unsigned long long)ph_acc[_k]);
+    if (lane == 0) for (int _k = 0; _k < SF_PHASE_WORDS; ++_k) atomicAdd(&g_phase[_k], (unsigned long long)ph_acc[_k]);
 #else
 #define PH_DECL
 #define PH(i)
@@ -1191,12 +1203,26 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
         const bool lane_hash = FAST && use_cm;
         if (lane_hash) {
             const uint64_t es0 = SALT_NEARBY_CHANGE_ENTITY ^ desc0(), es1 = SALT_NEARBY_SWAP_ENTITY ^ desc1();  // FAST: leaf 0 = nearby change, leaf 1 = nearby swap
-            const uint64_t salt = lane == 0 ? SALT_UNION_OFFSET : lane == 1 ? es0 : lane == 2 ? (es0 ^ STRIDE_SALT_MIX) : lane == 3 ? es1 : (es1 ^ STRIDE_SALT_MIX);
-            const FastMod fm2 = make_fastmod(2u);
-            FastMod f;
-            f.M = lane == 0 ? fm2.M : ((lane & 1u) ? fm_V.M : fm_V1.M);
-            f.n = lane == 0 ? fm2.n : ((lane & 1u) ? fm_V.n : fm_V1.n);
-            hashed = fastmod_u64(ctx.mixed_seed(salt), f);
+            if constexpr (RBATCH && SF_WAVE_SYM != 0) {
+                // The kernels with the lockstep round form the lane index again HERE: taken from `lane`, each lane's salt and divisor are computed
+                // before the step loop and carried through it in five vector registers, which those kernels do not have (the WPE 6 one went through
+                // scratch memory for them) -- a dozen selects per step instead.  The other kernels keep their statements, and so their code.
+                uint32_t hl = lane;
+                asm volatile("" : "+v"(hl));
+                const uint64_t salt = hl == 0 ? SALT_UNION_OFFSET : hl == 1 ? es0 : hl == 2 ? (es0 ^ STRIDE_SALT_MIX) : hl == 3 ? es1 : (es1 ^ STRIDE_SALT_MIX);
+                const FastMod fm2 = make_fastmod(2u);
+                FastMod f;
+                f.M = hl == 0 ? fm2.M : ((hl & 1u) ? fm_V.M : fm_V1.M);
+                f.n = hl == 0 ? fm2.n : ((hl & 1u) ? fm_V.n : fm_V1.n);
+                hashed = fastmod_u64(ctx.mixed_seed(salt), f);
+            } else {
+                const uint64_t salt = lane == 0 ? SALT_UNION_OFFSET : lane == 1 ? es0 : lane == 2 ? (es0 ^ STRIDE_SALT_MIX) : lane == 3 ? es1 : (es1 ^ STRIDE_SALT_MIX);
+                const FastMod fm2 = make_fastmod(2u);
+                FastMod f;
+                f.M = lane == 0 ? fm2.M : ((lane & 1u) ? fm_V.M : fm_V1.M);
+                f.n = lane == 0 ? fm2.n : ((lane & 1u) ? fm_V.n : fm_V1.n);
+                hashed = fastmod_u64(ctx.mixed_seed(salt), f);
+            }
         }
         const uint32_t first_leaf = lane_hash ? (uint32_t)__builtin_amdgcn_readlane((int)hashed, 0)
                                               : (n_leaves > 1 ? ctx.random_index((uint32_t)n_leaves, SALT_UNION_OFFSET) : 0u);
@@ -1346,6 +1372,11 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
         PH(1)
         // ---- (C) candidate rounds: fill the rings, replay one 64-wide batch, repeat -----------
         int done = 0;
+        // SYM: the lockstep round, offered once per step, at the first turn of the loop below (it shares that loop's generation
+        // helpers).  Equal max_nearby of at most half a batch, something to scan: at step start both leaves are live with the same `left` and
+        // empty rings, and they stay in lockstep for as long as every source emits max_nearby candidates.
+        constexpr bool SYM = RBATCH && SF_WAVE_SYM != 0;
+        [[maybe_unused]] bool lockstep = SYM && K0 == K1 && K0 <= 32u && total > 0;
         while (!done) {
             PH(4)
             // C1: generation.  Keep >= 32 candidates pending per live leaf (>= min(64, rc - K) when
@@ -1461,6 +1492,83 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                 } else
                     return node_slot.wide(word, node);
             };
+            // ---- the lockstep round.  While every source of both leaves emits max_nearby candidates the two cursors move together: the state of both
+            // leaves is ONE triple -- heads sym_h, tails sym_t, sources left sym_left -- and pulls = 2 sym_h, so the union's order puts first_leaf in
+            // the even lanes of every batch.  Fill: paired passes while fewer than 32 candidates per leaf are pending.  Batch: 64 lanes, 32 per leaf,
+            // all of them valid because the fill loop has just said so: no availability test, no mask.  (The general loop below keeps two cursors,
+            // forms `need` for each, and proves the 64 lanes available in every batch: about a fifth of a step's instructions at the default
+            // sizes.)  The round ends with the step -- the quota's cut -- or hands the cursors to the general loop for the rest of the step, when a
+            // source emits fewer (a short row, a neighbourhood without enough destinations) or no source is left with a batch still short. ----
+            if constexpr (SYM) {
+                if (lockstep) {
+                    lockstep = false;
+                    uint32_t sym_h = 0, sym_t = 0, sym_left = total, tA = 0, tB = 0;
+                    for (;;) {
+                        ISA_MARK("sym_fill_begin");
+                        bool leave = false;
+                        while (sym_t - sym_h < 32u) {
+                            tA = tB = sym_t;
+                            if (sym_left == 0) {
+                                leave = true;
+                                break;
+                            }
+                            ISA_MARK("pair_begin");
+                            GC(0)
+                            GC(8)
+                            uint32_t sym_left1 = sym_left;  // (one count for both leaves)
+#define SF_PAIR_TAIL0 sym_t
+#define SF_PAIR_TAIL1 sym_t
+#define SF_PAIR_LEFT0 sym_left
+#define SF_PAIR_LEFT1 sym_left1
+#include "sf_wave_pair_pass.inc"
+#undef SF_PAIR_TAIL0
+#undef SF_PAIR_TAIL1
+#undef SF_PAIR_LEFT0
+#undef SF_PAIR_LEFT1
+                            ISA_MARK("pair_end");
+                            if (emA != K0 || emB != K0) {
+                                tA += emA;
+                                tB += emB;
+                                leave = true;
+                                break;
+                            }
+                            sym_t += K0;
+                        }
+                        ISA_MARK("sym_fill_end");
+                        if (leave) break;
+                        wave_sync();
+                        ISA_MARK("sym_replay_begin");
+                        {
+                            constexpr bool valid = true;
+                            constexpr uint32_t nvalid = 64u;
+                            // the leaf of this lane's candidate is the same in every batch of the round; formed per batch all the same (two vector
+                            // instructions against a register carried through the step -- the WPE 6 kernels have none to spare)
+                            uint32_t fl = first_leaf, ln = lane;
+                            asm volatile("" : "+s"(fl), "+v"(ln));
+                            const uint32_t lf = (fl + ln) & 1u, idx = sym_h + (ln >> 1);
+                            uint32_t m0, m1, nconsumed = nvalid;
+                            uint64_t accmask;
+                            [[maybe_unused]] bool doable, acc, consumed;
+#include "sf_wave_replay_small.inc"
+                            accepted += (uint32_t)__popcll(accmask);
+                            if (done) {  // the cut: the step ends inside this batch
+                                pulls += nconsumed;
+                                break;
+                            }
+                        }
+                        sym_h += 32u;
+                        ISA_MARK("sym_replay_end");
+                    }
+                    // the cursors as the general loop keeps them (after the cut only `pulls` and the `left` counts are read again)
+                    pulls += 2u * sym_h;
+                    C0.head = C1.head = sym_h;
+                    C0.left = C1.left = sym_left;
+                    C0.tail = tA;
+                    C1.tail = tB;
+                    if (!done) { GC(9) }
+                    continue;
+                }
+            }
             const uint32_t single0 = cv.rc - K0 < 64u ? cv.rc - K0 : 64u, single1 = cv.rc - K1 < 64u ? cv.rc - K1 : 64u;
             ISA_MARK("fill_begin");
             for (;;) {
@@ -1471,201 +1579,15 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                 if (need0 && need1) {
                     ISA_MARK("pair_begin");
                     GC(0)
-                    // ---- paired pass: lanes 0-31 = the first 32 row entries of leaf 0's source, lanes
-                    // 32-63 = the first 32 of leaf 1's (its prefetch is stored rotated by 32 lanes) ----
-                    const bool hi = lane >= 32;
-                    const uint32_t seA = C0.se, spA = C0.sp, lenA = C0.len, kA = C0.k, sxA = C0.sx, tlA = C0.tail;
-                    const uint32_t seB = C1.se, spB = C1.sp, lenB = C1.len, kB = C1.k, sxB = C1.sx, tlB = C1.tail;
-                    // LEAN: each half blanks the lanes past its row now (resolve() left the entries raw)
-                    uint32_t l31 = lane & 31u;
-                    if constexpr (LEAN) asm volatile("" : "+v"(l31));  // (formed per pass: hoisted out of the loops, `l31 < dim` is a 64-bit mask in spill lanes)
-                    // (SF_SPEC_ROWS_FULL: both halves lie inside their rows and every entry is finite -- `have` is a literal, and with it the blanking
-                    // selects, `havemask`, its halves and the count arm of `ncv` below)
-                    const uint32_t key = LEAN ? (SF_SPEC_ROW_HAVE(false) ? half(C0.pk, C1.pk) : row_key(half(C0.pk, C1.pk), l31)) : (hi ? C1.pk : C0.pk);
-                    const bool have = SF_SPEC_ROW_HAVE(key != NBR_END);
-                    uint32_t nd = have ? (key & NBR_NODE_MASK) : 0u;  // unconditional read below (node 0 for the lanes past the row)
-                    uint32_t slot_word = 0;
-                    if constexpr (LEAN) {
-                        // the current keys are taken HERE, before the next sources' row loads issue: the only wait for a row load in the pass is this one,
-                        // for the loads of the pass before (the asm pins the order: the scheduler would otherwise sink the use below the new loads)
-                        asm volatile("" : "+v"(nd)::"memory");
-                        slot_word = node_slot.word(nd);  // ... and the table read is in flight across resolve()
-                    }
-                    C0.left -= 1;
-                    C0.o += 1;
-                    if (C0.left > 0) resolve(C0, 0);
-                    C1.left -= 1;
-                    C1.o += 1;
-                    if (C1.left > 0) resolve(C1, 1);
-                    if constexpr (!SMALL) st_sources += 2;
-                    uint32_t slot_any;
-                    if constexpr (LEAN)
-                        slot_any = slot_of(slot_word, nd);
-                    else
-                        slot_any = node_slot.get(nd);
-                    const uint32_t slot = have ? slot_any : NODE_NONE;
-                    NearbyItem it{0u, 0u, 0u, 0u};
-                    uint32_t mv0, tl, Kh, rq_off;  // this lane's half: source (entity << 16 | position), ring tail, max_nearby, ring offset in words
-                    if constexpr (LEAN) {
-                        // leaf 0 = nearby change (lanes 0-31), leaf 1 = nearby swap (lanes 32-63), as in the FAST item below, but every fact of a half picked
-                        // with half() and every predicate ONE unsigned compare of two selected words: no `hi` mask, no nested exec-mask regions.
-                        //   v0  change: another list, or dp - sp >= 2 (unsigned)     swap: intra dp > sp, inter rank > k
-                        //       as x > y with   intra: x = dp - (change ? sp : 0), y = change ? 1 : sp     inter: x = change ? ~0 : rank, y = change ? 0 : k
-                        //   v1  change only: dp + 1 == len2 and (another list or len != sp + 1), as one word that is zero exactly then
-                        const uint32_t sev = half(seA, seB), spv = half(spA, spB);
-                        mv0 = (sev << 16) | spv;
-                        tl = half(tlA, tlB);
-                        Kh = half(K0, K1);
-                        rq_off = hm & (cv.rc * 2u);
-                        // (every arm of a select below is a value already computed: a `?:` with work in an arm is compiled as an exec-mask region)
-                        const bool some = slot != NODE_NONE;
-                        const uint32_t r_any = slot >> 16, dp = slot & 0xFFFFu;
-                        const uint32_t r2 = some ? r_any : 0u;
-                        const uint32_t len2 = s_off[r2 + 1] - s_off[r2];
-                        uint32_t t;
-                        if constexpr (ARANK)
-                            t = RouteArith{half(perm_st0, perm_st1), half(perm_inv0, perm_inv1), (uint32_t)V, v_recip32}.word(r2);
-                        else
-                            t = rtab[r2 + (hm & (uint32_t)V)];
-                        const bool intra = r2 == sev;
-                        const uint32_t end_pay = (r2 << 16) | len2;
-                        const uint32_t xi = dp - (spv & ~hm), yi = half(1u, spv);
-                        const uint32_t xo = RT::rank(t) | ~hm, yo = kB & hm;
-                        const uint32_t xs = intra ? xi : xo, ys = intra ? yi : yo;
-                        const bool v0 = xs > ys;
-                        const uint32_t last = lenA ^ (spv + 1u);  // zero: the source is the last element of its list
-                        const uint32_t f = intra ? last : 1u;
-                        const uint32_t z1 = (((dp + 1u) ^ len2) | hm) | (1u - min(f, 1u));
-                        const bool v1 = z1 == 0u;
-                        const uint32_t b0 = v0 ? 1u : 0u, b1 = v1 ? 1u : 0u;
-                        const uint32_t wsum = b0 + b1;
-                        it.w = some ? wsum : 0u;
-                        const uint32_t len_or_dp = half(lenA, dp), ord_intra = v0 ? dp : len_or_dp, ord_inter = RT::inter_ord(t, dp);
-                        it.ord = intra ? ord_intra : ord_inter;
-                        const uint32_t end_or_slot = half(end_pay, slot);
-                        it.pay0 = v0 ? slot : end_or_slot;
-                        it.pay1 = end_pay;
-                    } else {
-                        const uint32_t se = hi ? seB : seA, sp = hi ? spB : spA, len = hi ? lenB : lenA, kk = hi ? kB : kA;
-                        mv0 = (se << 16) | sp;
-                        tl = hi ? tlB : tlA;
-                        Kh = hi ? K1 : K0;
-                        rq_off = hi ? cv.rc * 2u : 0u;
-                        RT rth;
-                        if constexpr (ARANK)
-                            rth = RouteArith{hi ? perm_st1 : perm_st0, hi ? perm_inv1 : perm_inv0, (uint32_t)V, v_recip32};
-                        else
-                            rth = RT{rtab + (hi ? V : 0)};
-                        if constexpr (FAST) {
-                            // leaf 0 = nearby change (lanes 0-31), leaf 1 = nearby swap (lanes 32-63): the two items of nearby_item_rt written as ONE, the
-                            // facts they share read once and the half a lane belongs to folded into the predicates (nearby_change.rs:133-195, nearby_swap.rs)
-                            const bool some = slot != NODE_NONE;
-                            const uint32_t r2 = some ? slot >> 16 : 0u, dp = slot & 0xFFFFu;
-                            const uint32_t len2 = s_off[r2 + 1] - s_off[r2];
-                            const uint32_t t = rth.word(r2);
-                            const bool intra = r2 == se;
-                            const uint32_t end_pay = (r2 << 16) | len2;
-                            // change: the slot itself unless it is the source's own or the one behind it (dp - sp is 0 or 1, unsigned); swap: a later position of
-                            // the source's list, or a list ranked after it
-                            const bool v0 = hi ? (intra ? dp > sp : RT::rank(t) > kk) : (!intra || dp - sp >= 2u);
-                            const bool v1 = !hi && dp + 1 == len2 && (!intra || len != sp + 1);  // change only: the end slot `len` probes element len - 1
-                            it.w = some ? (uint32_t)v0 + (uint32_t)v1 : 0u;
-                            it.ord = intra ? ((hi || v0) ? dp : len) : RT::inter_ord(t, dp);
-                            it.pay0 = (hi || v0) ? slot : end_pay;
-                            it.pay1 = end_pay;
-                        } else {
-                            const NearbyItem ic = nearby_item_rt(true, slot, se, sp, len, kk, s_off, rth);
-                            const NearbyItem is = nearby_item_rt(false, slot, se, sp, len, kk, s_off, rth);
-                            const bool lane_change = hi ? chg1 : chg0;
-                            it.w = lane_change ? ic.w : is.w;
-                            it.ord = lane_change ? ic.ord : is.ord;
-                            it.pay0 = lane_change ? ic.pay0 : is.pay0;
-                            it.pay1 = lane_change ? ic.pay1 : is.pay1;
-                        }
-                    }
-                    const uint64_t havemask = SF_SPEC_ROW_HAVEMASK(__ballot(have));
-                    // a group starts at the half's first lane and wherever the entry does not continue the previous one's distance.  LEAN: one compare,
-                    // key < 0x8000 (no NBR_SAME_FLAG, not NBR_END) in general and key < NBR_END at the half's first lane
-                    const uint64_t startmask = LEAN ? __ballot(key < NBR_END - min(l31, 1u) * (NBR_END - NBR_SAME_FLAG))
-                                                        : __ballot(have && (l31 == 0 || !(key & NBR_SAME_FLAG)));
-                    const uint32_t hvA = (uint32_t)havemask, hvB = (uint32_t)(havemask >> 32);
-                    const uint32_t stA = (uint32_t)startmask, stB = (uint32_t)(startmask >> 32);
-                    const bool moreA = hvA == 0xFFFFFFFFu && 32u < dim, moreB = hvB == 0xFFFFFFFFu && 32u < dim;
-                    // complete groups of each half (a half whose only group is still open contributes nothing)
-                    uint32_t ncA = 0, ncB = 0;
-                    uint64_t closedmask;
-                    bool closed;
-                    if constexpr (LEAN) {
-                        // every lane works its own half's count out of its half's two words (vector instructions; the scalar form was ~30 instructions of
-                        // s_flbit / s_bcnt1 / s_cselect / s_lshl per pass) -- the compare IS the closed mask; ncA / ncB are formed only where gen_rest is called
-                        const uint32_t hvv = half(hvA, hvB), stv = half(stA, stB);
-                        const uint32_t ncv = (hvv == 0xFFFFFFFFu && 32u < dim) ? 31u - (uint32_t)__clz(stv) : (uint32_t)__popc(hvv);
-                        closed = l31 < ncv;
-                        closedmask = __ballot(closed);
-                    } else {
-                        ncA = moreA ? 31u - (uint32_t)__clz(stA) : (uint32_t)__popc(hvA);
-                        ncB = moreB ? 31u - (uint32_t)__clz(stB) : (uint32_t)__popc(hvB);
-                        closedmask = (uint64_t)(ncA >= 32 ? 0xFFFFFFFFu : ((1u << ncA) - 1u)) |
-                                     ((uint64_t)(ncB >= 32 ? 0xFFFFFFFFu : ((1u << ncB) - 1u)) << 32);
-                        closed = (closedmask & lanebit) != 0;
-                    }
-                    const uint32_t wc = closed ? it.w : 0u;
-                    const uint64_t w1 = __ballot(wc == 1), w2 = __ballot(wc == 2);
-                    const uint32_t WcA = (uint32_t)__popc((uint32_t)w1) + 2u * (uint32_t)__popc((uint32_t)w2);
-                    const uint32_t WcB = (uint32_t)__popc((uint32_t)(w1 >> 32)) + 2u * (uint32_t)__popc((uint32_t)(w2 >> 32));
-                    if (WcA + WcB > 0) {
-                        const uint32_t pa = __builtin_amdgcn_mbcnt_lo((uint32_t)w1, 0u) + 2u * __builtin_amdgcn_mbcnt_lo((uint32_t)w2, 0u);
-                        const uint32_t pb = __builtin_amdgcn_mbcnt_hi((uint32_t)(w1 >> 32), 0u) + 2u * __builtin_amdgcn_mbcnt_hi((uint32_t)(w2 >> 32), 0u);
-                        int32_t pos = (int32_t)(LEAN ? half(pa, pb) : (hi ? pb : pa));
-                        const uint64_t nonstart = SF_SPEC_TIES(~startmask & closedmask);  // never crosses lane 32 (forced start)
-#ifdef SF_SPEC_TIE_KEY
-                        static_assert(!std::is_same<RT, RouteTab>::value, "SF_SPEC_TIE_KEY: the (rank, position) ordinals");
-                        if (nonstart) pos += tie_key_fix(startmask, nonstart, it.ord, wc);
-#else
-                        if (nonstart) {
-                            const uint32_t packed = (it.ord << 2) | wc;
-                            uint64_t run = nonstart;
-                            uint32_t p_dn = packed, p_up = packed;
-                            for (uint32_t d = 1; run != 0; ++d) {
-                                p_dn = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)p_dn, 0x130, 0xf, 0xf, false);  // wave_shl:1
-                                p_up = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)p_up, 0x138, 0xf, 0xf, false);  // wave_shr:1
-                                const bool same_up = (run & lanebit) != 0;
-                                const bool same_dn = ((run >> d) & lanebit) != 0;
-                                if (same_dn && (p_dn >> 2) < it.ord) pos += (int32_t)(p_dn & 3u);
-                                if (same_up && (p_up >> 2) > it.ord) pos -= (int32_t)(p_up & 3u);
-                                run &= nonstart << d;
-                            }
-                        }
-#endif
-                        uint32_t* rq = ring + rq_off;
-                        if (wc >= 1 && (uint32_t)pos < Kh) {
-                            const uint32_t qi = (tl + (uint32_t)pos) & RCM;
-                            rq[qi * 2] = mv0;
-                            rq[qi * 2 + 1] = it.pay0;
-                        }
-                        if (wc == 2 && (uint32_t)pos + 1 < Kh) {
-                            const uint32_t qi = (tl + (uint32_t)pos + 1) & RCM;
-                            rq[qi * 2] = mv0;
-                            rq[qi * 2 + 1] = it.pay1;
-                        }
-                    }
-                    uint32_t emA = WcA < K0 ? WcA : K0, emB = WcB < K1 ? WcB : K1;
-                    if (emA < K0 && moreA) {  // rare: leaf 0's source needs entries beyond its half
-                        GC(3)
-                        ISA_MARK("pair_rest_begin");
-                        if constexpr (LEAN) ncA = 31u - (uint32_t)__clz(stA);  // (moreA)
-                        const uint32_t jj = ncA + lane;
-                        emA = gen_rest(0, seA, spA, lenA, kA, sxA, tlA, jj < dim ? (uint32_t)nb.keys[(size_t)sxA * dim + jj] : NBR_END, ncA, K0 - emA, emA);
-                        ISA_MARK("pair_rest_end");
-                    }
-                    if (emB < K1 && moreB) {
-                        GC(4)
-                        ISA_MARK("pair_rest_begin");
-                        if constexpr (LEAN) ncB = 31u - (uint32_t)__clz(stB);  // (moreB)
-                        const uint32_t jj = ncB + lane;
-                        emB = gen_rest(1, seB, spB, lenB, kB, sxB, tlB, jj < dim ? (uint32_t)nb.keys[(size_t)sxB * dim + jj] : NBR_END, ncB, K1 - emB, emB);
-                        ISA_MARK("pair_rest_end");
-                    }
+#define SF_PAIR_TAIL0 C0.tail
+#define SF_PAIR_TAIL1 C1.tail
+#define SF_PAIR_LEFT0 C0.left
+#define SF_PAIR_LEFT1 C1.left
+#include "sf_wave_pair_pass.inc"
+#undef SF_PAIR_TAIL0
+#undef SF_PAIR_TAIL1
+#undef SF_PAIR_LEFT0
+#undef SF_PAIR_LEFT1
                     C0.tail = tlA + emA;
                     C1.tail = tlB + emB;
                     ISA_MARK("pair_end");
@@ -1733,106 +1655,7 @@ __global__ __launch_bounds__(64 * WPB, WPE) void k_list_search_wave(ListModel m,
                 uint64_t accmask = 0;
                 uint32_t nconsumed = nvalid;
                 if constexpr (SMALL) {
-                    // ---- delta-space replay (MODE 2): int32 level deltas against the step's current score ----
-                    // Every ring entry of a FAST kernel is a nearby candidate generated from the committed lists of THIS step: structurally doable
-                    // (eval_generated_small), so there is no doability test, and no exec-mask region either -- a lane past the valid ones re-prices
-                    // the batch's first candidate and is masked out of the decisions.
-                    int32_t dv[L];
-                    {
-                        const uint32_t lf0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)lf), idx0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)idx);
-                        const uint32_t lfq = valid ? lf : lf0;
-                        const uint32_t qi = (valid ? idx : idx0) & RCM;
-                        const uint32_t* rq = ring + ((size_t)lfq * cv.rc + qi) * 2;
-                        m0 = rq[0];
-                        m1 = rq[1];
-                        const uint32_t a = m0 >> 16, i = m0 & 0xFFFFu, b = m1 >> 16, j = m1 & 0xFFFFu;
-                        eval_generated_small<L, LT, COMPACT, OT, RBATCH>(m, lvl, s_visits, s_off, s_load, 1u - lfq, a, i, b, j, dv);  // FAST: leaf 0 = change, leaf 1 = swap; COMPACT reads the u16 matrix
-                    }
-                    doable = valid;
-                    // LateAcceptance: score >= last step score || score >= late score (late_acceptance.rs:89-125).  Two levels: the pair of int32 deltas
-                    // is ONE signed 64-bit key (hard x 2^32 + soft, |soft| < 2^31 keeps the order lexicographic), and the two tests are one compare
-                    // against the wave-uniform min(0, late - current)
-                    int64_t key = 0;
-                    if constexpr (L == 2) {
-                        key = (int64_t)(((uint64_t)(uint32_t)dv[0] << 32) + (uint64_t)(int64_t)dv[1]);
-                        acc = valid && key >= acc_thr;
-                    } else {
-                        acc = valid && (small_ge0<L>(dv) || small_ge<L>(dv, late_d));
-                    }
-                    accmask = __ballot(acc);
-                    // AcceptedCount quota (forager.rs:232-239): the step ends at the lane whose accepted candidate is the limit-th.  That lane exists
-                    // only in a batch with at least `remaining` accepted lanes -- the step's last one, one batch in ten at the default limit -- so one
-                    // wave-uniform compare on the batch's count (formed for `accepted` anyway) stands in front of the prefix count, the second
-                    // ballot and the re-masking; every other batch consumes its nvalid lanes, and `acc` (valid lanes only) is final as it stands.
-                    // `>=`: 64 accepted lanes with exactly 64 remaining do cut, at lane 63.  The same compare IS the forager's quit test.  Precondition:
-                    // FAST implies forager == FORAGER_ACCEPTED_COUNT (host-checked), whose forager_quits is `accepted >= limit`, and the host keeps
-                    // p.limit >= 1 for it; `accepted` never passes the limit.  A batch with at least `remaining` accepted lanes always holds the
-                    // limit-th accepted lane, so the cut fires in it, `accepted` becomes `limit` and the step ends; a batch with fewer leaves
-                    // `accepted` below the limit.  Cut and quit coincide: the step's end is decided here, not a second time at the batch's end.
-                    consumed = valid;
-                    if (!RBATCH || (uint32_t)__popcll(accmask) >= (uint32_t)SF_SPEC_LIMIT(p.limit) - accepted) {
-                        const uint32_t remaining = (uint32_t)SF_SPEC_LIMIT(p.limit) - accepted;
-                        const uint32_t pre = mbcnt64(accmask) + (acc ? 1u : 0u);
-                        const uint64_t cutmask = __ballot(acc && pre == remaining);
-                        nconsumed = cutmask ? (uint32_t)__ffsll((unsigned long long)cutmask) : nvalid;
-                        consumed = lane < nconsumed;
-                        acc = acc && consumed;
-                        accmask = __ballot(acc);
-                        if constexpr (RBATCH) {
-                            st_scored += nvalid - nconsumed;  // scored but not consumed (candidates_scored is added once per step, from `pulls`)
-                            done = 1;
-                        }
-                    }
-                    bool challenger;
-                    if constexpr (L == 2)
-                        challenger = acc && key >= best_key;
-                    else
-                        challenger = acc && small_ge<L>(dv, best_d);
-                    if (accmask && (!has_best || __ballot(challenger))) {
-                        // lexicographic maximum of the accepted lanes, level by level
-                        int32_t M[L];
-                        bool in_max = acc;
-#pragma unroll
-                        for (int kk = 0; kk < L; ++kk) {
-                            M[kk] = wave_max_i32(in_max ? dv[kk] : (int32_t)0x80000000);
-                            in_max = in_max && dv[kk] == M[kk];
-                        }
-                        // (two levels: the forager's best is best_key alone -- best_d[] would be the same value a second time in two more registers)
-                        int64_t Mkey = 0;
-                        if constexpr (L == 2) Mkey = (int64_t)(((uint64_t)(uint32_t)M[0] << 32) + (uint64_t)(int64_t)M[1]);
-                        bool ge, gt;
-                        if constexpr (L == 2) {
-                            ge = !has_best || Mkey >= best_key;
-                            gt = !has_best || Mkey > best_key;
-                        } else {
-                            ge = !has_best || small_ge<L>(M, best_d);
-                            gt = !has_best || !small_ge<L>(best_d, M);
-                        }
-                        if (ge) {
-                            const bool newmax = gt;
-                            const uint32_t eq_base = newmax ? 0u : equal_count;
-                            const uint64_t eq = __ballot(in_max);
-                            const uint32_t rank = mbcnt64(eq) + 1u;
-                            const uint64_t cntq = (uint64_t)(eq_base + rank);
-                            const bool pick = in_max && ((newmax && rank == 1) ||
-                                                         (p.random_ties && cntq > 1 && reservoir_pick(sseed, cntq)));
-                            const uint64_t pm = __ballot(pick);
-                            if (pm) {
-                                const int sel = 63 - __clzll((unsigned long long)pm);
-                                best_m0 = __shfl(m0, sel);
-                                best_m1 = __shfl(m1, sel);
-                                best_leaf = (int)__shfl(lf, sel);
-                            }
-                            if constexpr (L == 2) {
-                                best_key = Mkey;
-                            } else {
-#pragma unroll
-                                for (int kk = 0; kk < L; ++kk) best_d[kk] = M[kk];
-                            }
-                            equal_count = eq_base + (uint32_t)__popcll(eq);
-                            has_best = 1;
-                        }
-                    }
+#include "sf_wave_replay_small.inc"
                 } else {
                     ListDelta dl{0, 0, false};
                     if (valid) {

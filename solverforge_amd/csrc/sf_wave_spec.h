@@ -124,6 +124,13 @@ static int32_t wave_spec_knob() {  // read at every launch, like SF_AMD_WAVE_WPB
     return e ? (std::atoi(e) != 0 ? 1 : 0) : -1;
 }
 
+// SF_AMD_NO_WAVE_SYM: the unit without the lockstep round (-DSF_WAVE_SYM=0, as a Makefile build takes it through EXTRA).  Read once per process,
+// like SF_AMD_NO_COMPACT: the define is not part of the key, so the process-wide cache must never hold both kernels under one key.
+static bool wave_spec_no_sym() {
+    static const bool once = std::getenv("SF_AMD_NO_WAVE_SYM") != nullptr;
+    return once;
+}
+
 // The compiler's option list for a key: the Makefile's flags, the target, the include directories, the -D constants.
 static std::vector<std::string> wave_spec_options(const WaveSpecKey& k, const std::string& arch, const std::string& csrc, const std::string& rocm_include) {
     auto def = [](const char* name, int32_t v) { return std::string("-D") + name + "(x)=" + std::to_string(v); };
@@ -151,6 +158,7 @@ static std::vector<std::string> wave_spec_options(const WaveSpecKey& k, const st
         for (auto& x : {word("SF_SPEC_TIE_KEY", 1), word("SF_SPEC_RB", wave_spec_rb(k.V)), word("SF_SPEC_PB", wave_spec_pb(k.n_cap))}) o.push_back(x);
     if (k.index_x & SF_WSPEC_X_NO_TIES) o.push_back(word("SF_SPEC_NO_TIES", 1));
     if (k.index_x & SF_WSPEC_X_ROWS_FULL) o.push_back(word("SF_SPEC_ROWS_FULL", 1));
+    if (wave_spec_no_sym()) o.push_back("-DSF_WAVE_SYM=0");
     return o;
 }
 static std::string wave_spec_kernel_expr(const WaveSpecKey& k) {
