@@ -79,6 +79,12 @@ typedef enum sf_move_kind {
     SF_MOVE_LIST_PERMUTE = 9,  /* heuristic/move/list_kernel/permute.rs:22-72 (ListPermuteMove): the window [a_pos, b_pos) of list `a`
                                   (b = a, 2..8 positions) reordered by the value-th permutation of its positions in lexicographic
                                   order (nth_permutation, selector/list_kernel/permute.rs:260-272; value >= 1, 0 would be the identity) */
+    SF_MOVE_SCALAR_RUIN = 11,  /* selector/scalar_neighborhood/move/apply.rs:66-90,156-172,337-450 (RuntimeScalarRecipe::RuinRecreate, emitted by
+                                  the scalar ruin leaf).  A batch of up to eight 32-bit entity indices does not fit a record: `a` = the
+                                  candidate's ordinal in the step's ordered batch table, a_pos = its entity count, b = its first entity,
+                                  b_pos = value = 0; sf_get_scalar_ruin_table returns the batches and what the recreate gave every entity.
+                                  Comes back from sf_solve_step_traced / sf_step_generate only: sf_step_evaluate, sf_apply and sf_step_decide*
+                                  refuse it (SF_ERR_UNSUPPORTED) -- a ruin's result is expressed to them as the edits of the table */
     SF_MOVE_LIST_RUIN = 8      /* heuristic/move/list_kernel/ruin.rs:131-281 (one source list): list `a` loses the a_pos (1..6) elements
                                   at ascending positions packed 16 bits each into b (positions 0, 1), b_pos (2, 3), value (4, 5);
                                   every removed element is greedily re-inserted at its best (list, position).  Ruins of the critical-path
@@ -280,8 +286,11 @@ typedef enum sf_selector_kind {
                                       for slots with precedence hooks (policy/list.rs:24-33,62-93) */
     SF_SEL_NEARBY_SCALAR_CHANGE = 2048, /* scalar_neighborhood/cursor/change.rs:123-392 (NearbyChangeCursor); sf_selector_add_nearby_scalar */
     SF_SEL_NEARBY_SCALAR_SWAP = 4096,   /* scalar_neighborhood/cursor/swap.rs:162-414 (NearbySwapCursor); sf_selector_add_nearby_scalar */
-    SF_SEL_LIST_RUIN = 1024        /* selector/list_kernel/ruin.rs:38-144 + move/list_kernel/ruin.rs:131-281 (ruin and greedy recreate);
+    SF_SEL_LIST_RUIN = 1024,       /* selector/list_kernel/ruin.rs:38-144 + move/list_kernel/ruin.rs:131-281 (ruin and greedy recreate);
                                       sf_selector_add_ruin.  Last list leaf of the default policy (policy/list.rs:24-33,193-199) */
+    SF_SEL_SCALAR_RUIN = 32768     /* scalar_neighborhood/cursor.rs:144-175,234-256 + cursor/ruin.rs:13-141 + move/apply.rs:337-450
+                                      (RuinRecreateMoveSelector: ruin a random batch of entities, recreate them one after the other by first
+                                      fit or cheapest insertion); sf_selector_add_scalar_ruin.  No leaf of a default policy: configured only */
 } sf_selector_kind;
 
 typedef enum sf_selection_order { /* solverforge_config::SelectionOrder */
@@ -521,6 +530,34 @@ int32_t sf_union_configure(sf_ctx* ctx, int32_t selection_order, const int64_t* 
 int32_t sf_selector_add_ruin(sf_ctx* ctx, int32_t descriptor_index, int32_t variable_index, int32_t min_ruin_count,
                              int32_t max_ruin_count, int32_t moves_per_step, int32_t max_source_list_len,
                              int32_t skip_empty_destinations, const char* variable_name);
+
+/* scalar ruin-and-recreate leaf (MoveSelectorConfig::RuinRecreateMoveSelector, solverforge-config/src/move_selector.rs:53-54,299-328;
+ * scalar_neighborhood/spec.rs:122-139; defaults 2, 5, 10, none, FirstFit): per step `moves_per_step` batches of min..=max entities of the
+ * scalar class (both clamped to the entity count), drawn by a partial Fisher-Yates from the leaf's per-solve stream and ordered by the
+ * step's selection order.  A batch with an assigned entity (and, for a required variable, a candidate value for every assigned entity) is
+ * one candidate: its entities are unassigned in order, then placed in order -- FirstFit takes the first value of the entity's canonical
+ * list (cut to value_candidate_limit) that scores strictly above the state before the placement (a required variable: the first value),
+ * CheapestInsertion the best-scoring one (first of equals) when it is not below that state; an entity without such a value stays
+ * unassigned.  The candidate's score is the score after the recreate; it counts as one generated, evaluated and scored candidate.
+ * value_candidate_limit: -1 = none, 0 is a value (no candidates).  moves_per_step 0 = the default 10.  `variable_name` = the scalar
+ * variable's name: the stream is SmallRng::seed_from_u64(scoped_seed(random_seed + replica, descriptor_index, variable_name,
+ * "scalar_ruin_recreate_move_selector")) (cursor.rs:234-256), (re)seeded by sf_phase_start and drawn from at every cursor open; rand's
+ * generator and random_range are restated from the published algorithm, unpinned against the crate, as for the list ruin leaf.
+ * SF_ERR_INVALID: min_ruin_count < 1, max_ruin_count < min_ruin_count, a bad heuristic, a limit below -1, after sf_initialize.
+ * SF_ERR_UNSUPPORTED: max_ruin_count > 8, moves_per_step > 16, a second such leaf on the variable.  A union that holds the leaf runs in
+ * the generic engine whatever the model; refused at launch: TabuSearch, Variable Neighborhood Descent, a forced engine, a context with
+ * SF_C_CROSS_OWNER_MATCH, a dynamic nearby-scalar slot. */
+typedef enum sf_recreate_heuristic { SF_RECREATE_FIRST_FIT = 0, SF_RECREATE_CHEAPEST_INSERTION = 1 } sf_recreate_heuristic;
+int32_t sf_selector_add_scalar_ruin(sf_ctx* ctx, int32_t descriptor_index, int32_t variable_index, int32_t min_ruin_count,
+                                    int32_t max_ruin_count, int32_t moves_per_step, int32_t value_candidate_limit,
+                                    int32_t recreate_heuristic, const char* variable_name);
+/* The batch table of `replica`'s last traced (sf_solve_step_traced) or generated (sf_step_generate) step, in cursor order: per batch its
+ * entity count, its entities in batch order, whether the cursor emitted it, and for an emitted batch the value the recreate gave every
+ * entity (SF_NONE = left unassigned).  An SF_MOVE_SCALAR_RUIN record's `a` indexes it.  out_counts[16], out_entities[16 * 8],
+ * out_values[16 * 8], out_emitted[16]; rows past moves_per_step hold no batch (count 0, not emitted).  Entity indices are full 32-bit words.
+ * SF_ERR_INVALID when the last traced / generated step of the context was not this replica's, or there is none yet. */
+int32_t sf_get_scalar_ruin_table(sf_ctx* ctx, int32_t replica, int32_t* out_counts, int32_t* out_entities, int32_t* out_values,
+                                 int32_t* out_emitted);
 
 /* ---- Director surface -------------------------------------------------------------------- */
 /* ≙ first Director::calculate_score (initialize_all): builds per-replica aggregates.

@@ -12,7 +12,9 @@ from .director import (
     Forager,
     GpuScoreDirector,
     MoveKind,
+    Recreate,
     SelectionOrder,
+    SelectorKind,
     SolverConfig,
     UniCmp,
     UniLhs,

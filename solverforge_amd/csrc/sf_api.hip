@@ -60,6 +60,7 @@ struct SelectorSpec {
     int min_size = 1, max_size = 3;  // sublist leaves; ruin leaf: min / max ruin count
     int moves_per_step = 10, max_source_len = 0, skip_empty = 0;  // ruin leaf (ListRuinMoveSelectorConfig)
     std::string variable_name;                                    // ruin leaf: scoped_seed hashes the variable name
+    int value_limit = -1, recreate = 0;                           // scalar ruin leaf: value_candidate_limit (-1 = None), sf_recreate_heuristic
 };
 struct NearbyScalarSource {  // sf_selector_add_nearby_scalar: rows ranked by (distance, source order, candidate)
     bool present = false;
@@ -173,6 +174,8 @@ struct sf_ctx {
     int64_t* d_each = nullptr;           // [R][SF_EACH_WORDS] evaluate_each aggregates
     uint64_t* d_kopt_scratch = nullptr;  // [R][n_cap] distance keys of long routes (distance-pruned 3-opt leaf)
     uint64_t* d_ruin_rng = nullptr;      // [R][4] per-solve SmallRng state of the list ruin leaf
+    uint64_t* d_sruin_rng = nullptr;     // [R][4] per-solve SmallRng state of the scalar ruin-and-recreate leaf
+    int32_t* d_sruin_table = nullptr;    // [SRUIN_TAB_WORDS] batch table of the last traced / generated step (sf_get_scalar_ruin_table)
     uint32_t* d_mixed_ring = nullptr;    // [R][GL][GRC][2] candidate rings of the generic engine (+ [R][GL][GRC] side bytes)
     uint8_t* d_mixed_ringx = nullptr;
     int32_t* d_mixed_ringd = nullptr;    // [R][GL][GRC][2] trial deltas beside the rings (the FAST instantiations' scoring stage; allocated on first use)
@@ -818,6 +821,8 @@ static int ruin_phase_start(sf_ctx* ctx) {
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return SF_OK;
 }
+
+#include "sf_api_scalar_ruin.inc"  // the scalar ruin-and-recreate leaf: selector, streams at phase start, launch refusals, sf_get_scalar_ruin_table
 
 // ---- model assembly --------------------------------------------------------------------
 static int build_list_model(sf_ctx* ctx, int d) {
@@ -1814,6 +1819,7 @@ int32_t sf_phase_start(sf_ctx* ctx) {
     if ((rc = anneal_phase_start(ctx))) return rc;
     ctx->sp.acceptor = search_kind(ctx);  // the phase-start kernels run acceptor.phase_started of GreatDeluge / StepCountingHillClimbing, and vnd_phase_started
     if ((rc = ruin_phase_start(ctx))) return rc;
+    if ((rc = scalar_ruin_phase_start(ctx))) return rc;
     if (ctx->has_list_model)
         hipLaunchKernelGGL(k_list_phase_start, dim3(ctx->R), dim3(256), 0, ctx->stream, ctx->lm, ctx->sp);
     if (ctx->has_scalar_model)  // mixed: same committed score (aliased), adds the best snapshot of the values
@@ -1928,17 +1934,24 @@ static int launch_mixed(sf_ctx* ctx, SearchParams& p, int grid, bool trace) {
         for (int kind : {SF_SEL_LIST_PRECEDENCE, SF_SEL_LIST_PERMUTE,  // the precedence pair leads the list policy (policy/list.rs:24-33)
                          SF_SEL_NEARBY_LIST_CHANGE, SF_SEL_LIST_CHANGE, SF_SEL_NEARBY_LIST_SWAP, SF_SEL_LIST_SWAP, SF_SEL_SUBLIST_CHANGE,
                          SF_SEL_SUBLIST_SWAP, SF_SEL_LIST_REVERSE, SF_SEL_KOPT, SF_SEL_LIST_RUIN, SF_SEL_NEARBY_SCALAR_CHANGE,
-                         SF_SEL_NEARBY_SCALAR_SWAP, SF_SEL_SCALAR_CHANGE, SF_SEL_SCALAR_SWAP})  // nearby scalar rules precede the ordinary pair (policy.rs:104-108)
+                         SF_SEL_NEARBY_SCALAR_SWAP, SF_SEL_SCALAR_CHANGE, SF_SEL_SCALAR_SWAP,  // nearby scalar rules precede the ordinary pair (policy.rs:104-108)
+                         SF_SEL_SCALAR_RUIN})  // (no default policy declares it: a configured leaf goes last)
             for (auto& s : ctx->selectors)
                 if (s.kind == kind) ordered.push_back(&s);
     }
         for (const SelectorSpec* sp : ordered) {
             const SelectorSpec& s = *sp;
             const int kind = s.kind;
-            const bool is_list = kind != SF_SEL_SCALAR_CHANGE && kind != SF_SEL_SCALAR_SWAP && kind != SF_SEL_NEARBY_SCALAR_CHANGE && kind != SF_SEL_NEARBY_SCALAR_SWAP;
+            const bool is_list = kind != SF_SEL_SCALAR_CHANGE && kind != SF_SEL_SCALAR_SWAP && kind != SF_SEL_NEARBY_SCALAR_CHANGE && kind != SF_SEL_NEARBY_SCALAR_SWAP &&
+                                 kind != SF_SEL_SCALAR_RUIN;
             if (is_list ? (!ctx->has_list_model || s.desc != ctx->list_desc) : (!ctx->has_scalar_model || s.desc != ctx->scalar_desc))
                 continue;
             if (gl.n >= GL) return fail(ctx, SF_ERR_UNSUPPORTED, "too many leaves for the generic engine");
+            if (kind == SF_SEL_SCALAR_RUIN) {  // (launch_search has checked what such a launch cannot run, and takes the traced instantiation)
+                if (has_scalar_ruin_leaf(gl.kind, gl.n)) return fail(ctx, SF_ERR_UNSUPPORTED, "one scalar ruin leaf per union");
+                if (!trace) return fail(ctx, SF_ERR_INVALID, "scalar ruin leaf: the traced instantiation carries it");
+                gl.sruin = SRuinParams{s.min_size, s.max_size, s.moves_per_step, s.value_limit, s.recreate, ctx->d_sruin_rng, ctx->d_sruin_table};
+            }
             if (kind == SF_SEL_NEARBY_LIST_CHANGE || kind == SF_SEL_NEARBY_LIST_SWAP) {
                 if (!wave_engine_possible(ctx)) return fail(ctx, SF_ERR_UNSUPPORTED, "nearby leaves need the neighbour index (matrix meter, <= 16384 nodes)");
                 if (gl.has_nearby >= 2) return fail(ctx, SF_ERR_UNSUPPORTED, "at most two nearby leaves per union");
@@ -2074,6 +2087,13 @@ static int launch_search(sf_ctx* ctx, SearchParams& p, int grid, bool trace) {
     if (p.acceptor == VND_KIND) {
         if (ctx->sp.acceptor != VND_KIND) return fail(ctx, SF_ERR_INVALID, "variable neighborhood descent: sf_phase_start after sf_solver_configure_vnd");
         if (const char* why = vnd_launch_refusal(ctx)) return fail(ctx, SF_ERR_UNSUPPORTED, why);
+        return launch_mixed(ctx, p, grid, true);
+    }
+    // The scalar ruin-and-recreate leaf (sf_scalar_ruin.h) lives in the generic engine's TRACE instantiations: a union that holds it runs there
+    // whatever the model, with no replica traced unless the caller traces one
+    if (scalar_ruin_selector(ctx)) {
+        if (!ctx->d_sruin_rng) return fail(ctx, SF_ERR_INVALID, "scalar ruin leaf: sf_phase_start seeds its stream first");
+        if (const char* why = scalar_ruin_launch_refusal(ctx)) return fail(ctx, SF_ERR_UNSUPPORTED, why);
         return launch_mixed(ctx, p, grid, true);
     }
     // the 2-leaf nearby union has its own engines; every other union runs in the generic N-leaf engine

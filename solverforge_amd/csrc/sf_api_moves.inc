@@ -51,6 +51,8 @@ int32_t sf_step_evaluate(sf_ctx* ctx, int32_t replica, const sf_move_t* moves, i
     if (ctx->xown_level >= 0)
         for (int64_t i = 0; i < n; ++i)
             if (moves[i].kind == SF_MOVE_LIST_RUIN) return fail(ctx, SF_ERR_UNSUPPORTED, "the join of the two planning classes is not priced by a ruin's recreate");
+    for (int64_t i = 0; i < n; ++i)
+        if (moves[i].kind == SF_MOVE_SCALAR_RUIN) return fail(ctx, SF_ERR_UNSUPPORTED, SCALAR_RUIN_RECORD_REFUSAL);
     if (n == 0) return SF_OK;
     Scratch<sf_move_t> d_rec;
     Scratch<int64_t> d_sc;
@@ -227,6 +229,8 @@ static int32_t step_decide_impl(sf_ctx* ctx, int32_t replica, const sf_move_t* e
     for (int64_t i = 0; i < n; ++i)
         if (offsets[i + 1] < offsets[i]) return fail(ctx, SF_ERR_INVALID, "offsets must not decrease");
     if (n > 0 && offsets[n] > 0 && !edits) return fail(ctx, SF_ERR_INVALID, "edits is NULL");
+    for (int64_t k = 0; n > 0 && k < offsets[n]; ++k)
+        if (edits[k].kind == SF_MOVE_SCALAR_RUIN) return fail(ctx, SF_ERR_UNSUPPORTED, SCALAR_RUIN_RECORD_REFUSAL);
     int rc = alloc_search(ctx);
     if (rc) return rc;
     SearchParams p = ctx->sp;
@@ -378,6 +382,7 @@ int32_t sf_apply(sf_ctx* ctx, int32_t replica, const sf_move_t* mv) {
     if (!ctx || !ctx->initialized || !mv || replica < 0 || replica >= ctx->R)
         return fail(ctx, SF_ERR_INVALID, "bad sf_apply arguments");
     if (ctx->xown_level >= 0 && mv->kind == SF_MOVE_LIST_RUIN) return fail(ctx, SF_ERR_UNSUPPORTED, "the join of the two planning classes is not priced by a ruin's recreate");
+    if (mv->kind == SF_MOVE_SCALAR_RUIN) return fail(ctx, SF_ERR_UNSUPPORTED, SCALAR_RUIN_RECORD_REFUSAL);
     int rc = alloc_search(ctx);
     if (rc) return rc;
     if (mv->kind == SF_MOVE_LIST_RUIN) {  // committed ruin + recreate: its own kernel

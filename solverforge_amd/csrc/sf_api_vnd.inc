@@ -16,7 +16,8 @@ extern "C" int32_t sf_solver_configure_vnd(sf_ctx* ctx) {
 static int vnd_neighbourhoods(const sf_ctx* ctx) {
     int n = 0;
     for (const auto& s : ctx->selectors) {
-        const bool is_list = s.kind != SF_SEL_SCALAR_CHANGE && s.kind != SF_SEL_SCALAR_SWAP && s.kind != SF_SEL_NEARBY_SCALAR_CHANGE && s.kind != SF_SEL_NEARBY_SCALAR_SWAP;
+        const bool is_list = s.kind != SF_SEL_SCALAR_CHANGE && s.kind != SF_SEL_SCALAR_SWAP && s.kind != SF_SEL_NEARBY_SCALAR_CHANGE && s.kind != SF_SEL_NEARBY_SCALAR_SWAP &&
+                             s.kind != SF_SEL_SCALAR_RUIN;
         if (is_list ? (ctx->has_list_model && s.desc == ctx->list_desc) : (ctx->has_scalar_model && s.desc == ctx->scalar_desc)) n += 1;
     }
     return n;
@@ -41,6 +42,8 @@ static const char* vnd_launch_refusal(sf_ctx* ctx) {
     for (const auto& s : ctx->selectors) {
         if (s.kind == SF_SEL_LIST_RUIN)
             return "variable neighborhood descent: the ruin leaf (its per-solve random stream and step-start trials have no Original-order meaning)";
+        if (s.kind == SF_SEL_SCALAR_RUIN)
+            return "variable neighborhood descent: the scalar ruin leaf (its per-solve random stream and step-start trials have no Original-order meaning)";
         if (s.kind == SF_SEL_LIST_PRECEDENCE)
             return "variable neighborhood descent: the critical-path precedence leaf (its gated multi-swaps and step analysis are not a plain neighbourhood)";
     }

@@ -63,9 +63,11 @@ struct GenericPlan {
 // prec_words = the precedence constraint's node count when its Kahn scratch lives in the slice, else 0 (and then no groups either).
 // The carve's ruin argument: 3 = the list-preserving recreate only (the FAST kernels), 2 = + 16-bit leg tables, 1 = the general path.
 static size_t generic_slice_bytes(const GenericShape& s, int value_bytes, int prec_words, int prec_groups, bool nodeg) {
+    // the scalar ruin-and-recreate leaf's block: the kernel reserves it in its TRACE instantiations when the union holds the leaf (kind 32768)
+    const bool scalar_ruin = s.trace != 0 && has_scalar_ruin_leaf(s.kind, s.n_leaves);
     auto total = [&](auto vt) {
         return GCarve<decltype(vt)>(s.n_scalar, s.V, s.n_cap, s.has_nearby ? s.dim : 0, s.kopt_nearby, s.n_leaves, s.has_ruin ? (nodeg ? 3 : (s.leg16 ? 2 : 1)) : 0,
-                                    s.dim, prec_words, s.tables ? s.n_values : 0, s.tables && s.run_level >= 0 ? s.run_P : 0, prec_groups, nodeg).total;
+                                    s.dim, prec_words, s.tables ? s.n_values : 0, s.tables && s.run_level >= 0 ? s.run_P : 0, prec_groups, nodeg, scalar_ruin).total;
     };
     return value_bytes == 1 ? total(int8_t{}) : total(int16_t{});
 }

@@ -37,6 +37,7 @@ constexpr uint32_t GRC = 128;  // ring capacity per leaf
 #define SF_MIXED_RING_LDS 0  // diagnostics: 1 keeps the candidate rings in the replica's LDS slice (the round-2 layout)
 #endif
 constexpr size_t RUIN_LDS_BYTES = 8 * 8 + 16 * (8 * 2 + 4 * 8) + 128;  // == RuinLds::bytes (sf_ruin.h)
+constexpr size_t SRUIN_LDS_BYTES = 4 * 8 + 16 * 4 * 8 + 2 * 16 * 8 * 4 + 2 * 16 * 4 + 8 * 4;  // == SRuinLds::bytes (sf_scalar_ruin.h)
 
 constexpr uint64_t SALT_LC_ENTITY = 0x1157C4A46E000001ULL, SALT_LC_SOURCE = 0x1157C4A46E000002ULL;
 constexpr uint64_t SALT_LC_INTRA = 0x1157C4A46E000003ULL, SALT_LC_INTER = 0x1157C4A46E000004ULL;
@@ -72,6 +73,20 @@ struct RuinParams {  // list ruin leaf (sf_ruin.h)
     int32_t skip_empty;
     uint64_t* rng;  // [R][4] per-solve SmallRng state of the leaf
 };
+
+struct SRuinParams {  // scalar ruin-and-recreate leaf (sf_scalar_ruin.h; kind 32768, the TRACE instantiations carry it)
+    int32_t min_count, max_count, moves_per_step;
+    int32_t limit;      // value_candidate_limit, -1 = None
+    int32_t heuristic;  // sf_recreate_heuristic: 0 FirstFit, 1 CheapestInsertion
+    uint64_t* rng;      // [R][4] per-solve SmallRng state of the leaf
+    int32_t* table;     // [SRUIN_TAB_WORDS] the traced replica's batch table of its last step (sf_get_scalar_ruin_table)
+};
+__host__ __device__ inline bool has_scalar_ruin_leaf(const int32_t (&kind)[GL], int n) {  // (compile-time l: no dynamic indexing of the kernarg block)
+    bool has = false;
+#pragma unroll
+    for (int l = 0; l < GL; ++l) has = has || (l < n && kind[l] == 32768);
+    return has;
+}
 
 struct GLeaves {
     int32_t n;
@@ -117,6 +132,7 @@ struct GLeaves {
     int64_t xown_weight;
     uint16_t* xown_tab;
     uint32_t* node_tab;      // [R][dim] node -> (list << 16 | position) in HBM: the FAST + ruin instantiation keeps it out of the LDS slice (12 replicas per CU)
+    SRuinParams sruin;       // scalar ruin-and-recreate leaf (kind 32768): parameters, per-solve stream, trace table
 };
 
 // u16 entries of RuinFast::slot: the slot table of sf_ruin.h (n_cap + V) and the arena of sf_ruin_v2.h, which never overflows at n_cap + 21
@@ -124,7 +140,7 @@ struct GLeaves {
 __host__ __device__ inline size_t ruin_arena_cap(int n_cap, int V) { return (size_t)n_cap + (size_t)(V > 24 ? V : 24); }
 template <class VT>
 struct GCarve {
-    size_t ring, ringx, load, off, visits, vals, tsum, tcnt, tpt, nstmp, node, slotbase, routeat, rankof, spvec, kopt, ruin, ruin_fast, prec, pgrp, leaftab, total;
+    size_t ring, ringx, load, off, visits, vals, tsum, tcnt, tpt, nstmp, node, slotbase, routeat, rankof, spvec, kopt, ruin, ruin_fast, sruin, prec, pgrp, leaftab, total;
     // dim_nearby = node-id bound when the union has nearby leaves (node -> slot table + two leaves'
     // entity-order tables), else 0
     // n_leaves rings only: the LDS slice decides how many replicas a CU holds
@@ -135,7 +151,7 @@ struct GCarve {
     // has_ruin 3: the list-preserving recreate only (sf_ruin_v2.h; the FAST instantiation): edge table + list-end edges + arena, no matrix row
     // node_global: the node -> slot table lives in HBM (GLeaves::node_tab)
     __host__ __device__ __forceinline__ GCarve(int n_scalar, int V, int n_cap, int dim_nearby, int kopt_nearby = 0, int n_leaves = GL, int has_ruin = 0, int dim = 0,
-                               int prec_words = 0, int n_table = 0, int run_P = 0, int prec_groups = 0, bool node_global = false) {
+                               int prec_words = 0, int n_table = 0, int run_P = 0, int prec_groups = 0, bool node_global = false, bool scalar_ruin = false) {
         size_t o = 0;
         ring = o;  // the candidate rings live in HBM (GLeaves::ring / ringx) unless SF_MIXED_RING_LDS
         o = align_up(o + (SF_MIXED_RING_LDS ? sizeof(uint32_t) * 2 * GRC * n_leaves : 0), 16);
@@ -173,6 +189,8 @@ struct GCarve {
         o = align_up(o + (has_ruin ? RUIN_LDS_BYTES + sizeof(uint32_t) * (V + 1) : 0), 16);  // + the slot prefix of a recreate round
         ruin_fast = o;  // edge[dim], row[dim], edge_end[V], slot[n_cap + V]
         o = align_up(o + (has_ruin >= 2 ? sizeof(uint16_t) * ((has_ruin == 2 ? 2 : 1) * (size_t)dim + (size_t)V + ruin_arena_cap(n_cap, V)) : 0), 16);
+        sruin = o;  // scalar ruin-and-recreate leaf: stream, batch table, trial scores (SRuinLds); only when the union holds the leaf
+        o = align_up(o + (scalar_ruin ? SRUIN_LDS_BYTES : 0), 16);
         prec = o;  // earliest start, in-degree, queue, list successor of the precedence constraint's Kahn pass
         o = align_up(o + prec_lds_scratch_bytes(prec_words), 16);  // (i32, i32, u16, u16)
         pgrp = o;  // grouped trial evaluator (sf_prec_group.h): committed successor / in-degree + per-trial scratch
@@ -295,6 +313,7 @@ __device__ __forceinline__ int32_t xown_list_delta(int kind, uint32_t m0, uint32
 }  // namespace sf
 #include "sf_ruin.h"
 #include "sf_ruin_v2.h"
+#include "sf_scalar_ruin.h"
 namespace sf {
 
 // workgroups of 4 waves: 2 resident workgroups per CU = 2 waves per SIMD (<= 256 VGPRs)
@@ -397,7 +416,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
     constexpr bool NODEG = FAST && (RUIN || SF_MIXED_FAST_NODEG != 0);
     const GCarve<VT> cv((int)ns, V, has_list ? lm.n_cap : 0, has_nearby ? lm.dim : 0, gl.kopt_nearby, gl.n, RUIN ? (FAST ? 3 : (lm.leg16 ? 2 : 1)) : 0, lm.dim,
                         PREC && gl.prec_lds ? gl.prec.n : 0, tables ? sm.n_values : 0, tables && sm.run_level >= 0 ? sm.run_P : 0,
-                        PREC && gl.prec_lds ? gl.prec_groups : 0, NODEG);
+                        PREC && gl.prec_lds ? gl.prec_groups : 0, NODEG, TRACE && has_scalar_ruin_leaf(gl.kind, gl.n));
     unsigned char* mem = smem + (size_t)wave_in_group * cv.total;
     PH_DECL
     PgrpStatic pgs{};  // the same arrays behind typed LDS pointers
@@ -530,6 +549,15 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
         if (lane < 4) rl.prng[lane] = gl.ruin.rng[(size_t)r * 4 + lane];
         wave_sync();
     }
+    // scalar ruin-and-recreate leaf (sf_scalar_ruin.h; the TRACE instantiations carry it): its block of the slice, its per-solve stream
+    [[maybe_unused]] bool sruin_on = false;
+    if constexpr (TRACE) sruin_on = has_scalar && has_scalar_ruin_leaf(gl.kind, gl.n);
+    [[maybe_unused]] const SRuinLds srl(mem + cv.sruin);
+    if constexpr (TRACE)
+        if (sruin_on) {
+            if (lane < 4) srl.prng[lane] = gl.sruin.rng[(size_t)r * 4 + lane];
+            wave_sync();
+        }
 
     int64_t cur[L], best_sol[L];
 #pragma unroll
@@ -1334,6 +1362,28 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                 PHS(3)
             }
         }
+        if constexpr (TRACE)
+            if (sruin_on) {  // scalar ruin-and-recreate leaf: open the cursor (the step's batches from the per-solve stream), then score every emitted batch
+                const uint32_t n_emit = sruin_open_cursor(gl.sruin, srl, sm, s_vals, ctx, identity, !dry_run, lane);
+                for (int l = 0; l < nl; ++l)
+                    if (lt.geti(l, LeafTab::KIND) == 32768) lt.put_gen(l, GGen{0, 0, 0, 0, n_emit, 0, n_emit == 0});
+                uint32_t priced = 0;
+                for (uint32_t b = 0; b < (uint32_t)gl.sruin.moves_per_step; ++b)
+                    if (uni(srl.emit[b]) != 0u) sruin_trial<L>(gl.sruin, srl, sm, s_vals, t_cnt, t_sum, tables, lbv, cur, b, lane, priced);
+                st_scored += priced;  // the placements' inner trials: candidates_scored only
+                if (tracing) {  // the table of this step for sf_get_scalar_ruin_table
+                    int32_t* tab = gl.sruin.table;
+                    for (uint32_t t = lane; t < SRUIN_MAX_MOVES * SRUIN_MAX_COUNT; t += 64) {
+                        tab[SRUIN_TAB_ENT + t] = (int32_t)srl.ent[t];
+                        tab[SRUIN_TAB_VAL + t] = srl.val[t];
+                    }
+                    if (lane < SRUIN_MAX_MOVES) {
+                        tab[SRUIN_TAB_CNT + lane] = (int32_t)srl.cnt[lane];
+                        tab[SRUIN_TAB_EMIT + lane] = (int32_t)srl.emit[lane];
+                    }
+                    if (lane == 0) tab[SRUIN_TAB_REPLICA] = r, tab[SRUIN_TAB_REPLICA + 1] = 1;
+                }
+            }
         // union scheduler (vec_union.rs:190-365): StratifiedRandom with equal weights when > 1 leaf
         const uint32_t u_off = nl > 1 ? ctx.random_index((uint32_t)nl, SALT_UNION_OFFSET) : 0u;
         const uint32_t u_str = nl > 1 ? ctx.random_stride((uint32_t)nl, SALT_UNION_STRIDE) : 1u;
@@ -2014,6 +2064,15 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                                 }
                             }
                         }
+                    } else if (TRACE && kind == 32768) {  // ---- scalar ruin-and-recreate (cursor/ruin.rs:87-141): the emitted batches in table order, scored when the step started ----
+                        if (g.a != 0) {
+                            g.done = 1;
+                            break;
+                        }
+                        keep = lane < (uint32_t)gl.sruin.moves_per_step && srl.emit[lane] != 0u;  // (moves_per_step <= 16)
+                        w0 = lane;  // the ring entry names the ordinal in the step's batch table
+                        g.a = 1;
+                        g.done = 1;
                     } else if (RUIN && kind == 1024) {  // ---- list ruin (list_kernel/ruin.rs:127-144): one candidate per call, scored right here ----
                         if (g.a >= (uint32_t)gl.ruin.moves_per_step) {
                             g.done = 1;
@@ -2156,7 +2215,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                             }
                         }
                     }
-                    if (PREC && plf_policy && kind >= 4 && kind != 512 && kind != 1024 && kind != 2048 && kind != 4096 && kind != 16384) {
+                    if (PREC && plf_policy && kind >= 4 && kind != 512 && kind != 1024 && kind != 2048 && kind != 4096 && kind != 16384 && !(TRACE && kind == 32768)) {
                         // runtime slot with precedence hooks: intra-list candidates that close a cycle through the route graph never reach the ring
                         uint64_t chk = __ballot(keep && (kind == 64 || kind == 8192 || (w0 >> 16) == (w1 >> 16)));
                         cache_pen = INT64_MIN, cache_mk = 0;
@@ -2440,6 +2499,10 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                             for (int kk = 0; kk < L; ++kk)
                                 if (kk == gl.xown_level) sc.v[kk] = wsub(sc.v[kk], (int64_t)((uint64_t)gl.xown_weight * (uint64_t)dx));
                         }
+                    } else if (TRACE && my_kind == 32768) {  // scalar ruin-and-recreate: scored when the step started; every emitted batch is doable
+                        doable = true;
+#pragma unroll
+                        for (int kk = 0; kk < L; ++kk) sc.v[kk] = srl.score[(size_t)m0 * 4 + kk];
                     } else if (PREC && my_kind == 16384) {  // critical-path leaf: scored when it was generated
                         doable = true;
 #pragma unroll
@@ -2490,10 +2553,10 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                 for (int kk = 0; kk < L; ++kk) curv.v[kk] = cur[kk];
                 doable = doable && valid;
                 if (PREC) {
-                    uint64_t todo = __ballot(doable && my_kind >= 4 && my_kind != 1024 && my_kind != 16384);
+                    uint64_t todo = __ballot(doable && my_kind >= 4 && my_kind != 1024 && my_kind != 16384 && !(TRACE && my_kind == 32768));
                     if (plf_policy) {  // the route-graph filter evaluated the intra-list candidates when they were generated
                         bool cached = false;
-                        if (doable && my_kind >= 4 && my_kind != 1024 && my_kind != 16384) {
+                        if (doable && my_kind >= 4 && my_kind != 1024 && my_kind != 16384 && !(TRACE && my_kind == 32768)) {
                             const size_t ci_ = ((size_t)my_leaf * GRC + (my_idx & (GRC - 1))) * 2;
                             const int64_t cp = plf_cache[ci_];
                             if (cp != INT64_MIN) {
@@ -2686,6 +2749,13 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                             tm[3] = my_kind == 1 ? 0 : (int32_t)m1;
                             tm[4] = 0;
                             tm[5] = my_kind == 1 ? (int32_t)m1 : -1;
+                        } else if (TRACE && my_kind == 32768) {  // (11, ordinal in the batch table, entity count, first entity, 0, 0): sf_get_scalar_ruin_table has the rest
+                            tm[0] = 11;
+                            tm[1] = (int32_t)m0;
+                            tm[2] = (int32_t)srl.cnt[m0];
+                            tm[3] = (int32_t)srl.ent[(size_t)m0 * SRUIN_MAX_COUNT];
+                            tm[4] = 0;
+                            tm[5] = 0;
                         } else if (PREC && my_kind == 16384) {
                             // decoded one candidate at a time below (the decoders are wave-uniform)
                         } else if (RUIN && my_kind == 1024) {  // a = list, a_pos = count, six 16-bit positions in b / b_pos / value
@@ -2784,6 +2854,18 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                     }
                 }
                 wave_sync();
+            } else if (TRACE && kind == 32768) {  // committed scalar ruin: the result values its trial recorded, through the unassign-then-assign path
+                if (tracing && lane == 0) {
+                    p.trace_applied[0] = 1;
+                    if ((int64_t)best_ti < p.trace_cap) p.trace_flags[best_ti] |= 4;  // Selected + Applied
+                    p.trace_applied[1] = 11;
+                    p.trace_applied[2] = (int32_t)a;
+                    p.trace_applied[3] = (int32_t)srl.cnt[a];
+                    p.trace_applied[4] = (int32_t)srl.ent[(size_t)a * SRUIN_MAX_COUNT];
+                    p.trace_applied[5] = 0;
+                    p.trace_applied[6] = 0;
+                }
+                sruin_commit(srl, sm, s_vals, t_cnt, t_sum, tables, a, lane);
             } else if (PREC && kind == 16384) {  // critical-path leaf: decode the pick again (the analysis tables are the step's), apply it
                 PlfMove pm_;
                 plf_decode(a, b, pm_);
@@ -2879,7 +2961,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                     ring_sync();
                 }
             }
-            if (PREC && kind > 2) {  // a list move was committed: the HBM copy the trials undo from, and the constraint's committed state
+            if (PREC && kind > 2 && !(TRACE && kind == 32768)) {  // a list move was committed: the HBM copy the trials undo from, and the constraint's committed state
                 const uint32_t tot = uni(s_off[V]);
                 for (uint32_t t = lane; t < tot; t += 64) g_visits[t] = s_visits[t];
                 for (uint32_t t = lane; t <= (uint32_t)V; t += 64) g_off[t] = s_off[t];
@@ -2950,6 +3032,8 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
     if (!dry_run) {
         if (annealing) sa_store(saw, p.sa, r, lane);
         if (RUIN && lane < 4) gl.ruin.rng[(size_t)r * 4 + lane] = rl.prng[lane];
+        if constexpr (TRACE)
+            if (sruin_on && lane < 4) gl.sruin.rng[(size_t)r * 4 + lane] = srl.prng[lane];
         if (best_pending) {  // the launch ends in a best state: its deferred snapshot
             if (has_list) {
                 const uint32_t tot = uni(s_off[V]);

@@ -23,6 +23,11 @@ class MoveKind:
     LIST_RUIN = 8  # a = list, a_pos = count, six 16-bit ascending positions in b / b_pos / value
     LIST_MULTI_SWAP = 10  # a = swaps; a_pos / b / b_pos = (list | first << 16) per swap; value = second - first, one byte per swap
     LIST_PERMUTE = 9  # a = b = list, [a_pos, b_pos) = the window, value = rank of the permutation (lexicographic, >= 1)
+    SCALAR_RUIN = 11  # a = ordinal in the step's batch table (scalar_ruin_table), a_pos = entity count, b = first entity
+
+
+class Recreate:  # sf_recreate_heuristic: solverforge_config::RecreateHeuristicType
+    FIRST_FIT, CHEAPEST_INSERTION = 0, 1
 
 
 class UniLhs:  # sf_uni_lhs
@@ -91,6 +96,7 @@ class SelectorKind:
     NEARBY_SCALAR_CHANGE, NEARBY_SCALAR_SWAP = 2048, 4096
     LIST_PERMUTE = 8192
     LIST_PRECEDENCE = 16384
+    SCALAR_RUIN = 32768
 
 
 @dataclass
@@ -302,6 +308,30 @@ class GpuScoreDirector:
         """List ruin leaf (ListRuinMoveSelectorConfig defaults); max_source_list_len 0 = None."""
         check(self._L.sf_selector_add_ruin(self._h, descriptor_index, variable_index, min_ruin_count, max_ruin_count, moves_per_step,
                                            max_source_list_len, int(skip_empty_destinations), variable_name.encode()), self._h)
+
+    def add_scalar_ruin_selector(self, descriptor_index, variable_index=0, min_ruin_count=2, max_ruin_count=5, moves_per_step=10,
+                                 value_candidate_limit=None, recreate=Recreate.FIRST_FIT, variable_name="value"):
+        """Scalar ruin-and-recreate leaf (RuinRecreateMoveSelectorConfig defaults): per step moves_per_step (<= 16) batches of
+        min..=max (<= 8) entities, unassigned and then placed one after the other by first fit or cheapest insertion over the first
+        value_candidate_limit (None = all) values of each entity's canonical list.  Generic engine; see sf_selector_add_scalar_ruin."""
+        check(self._L.sf_selector_add_scalar_ruin(self._h, descriptor_index, variable_index, min_ruin_count, max_ruin_count, moves_per_step,
+                                                  -1 if value_candidate_limit is None else int(value_candidate_limit), int(recreate),
+                                                  variable_name.encode()), self._h)
+        self._scalar_ruin_moves_per_step = moves_per_step or 10  # (0 = the default)
+
+    def scalar_ruin_table(self, replica=0):
+        """The batch table of the replica's last traced or generated step, in cursor order: list of dicts {"entities": [...],
+        "emitted": bool, "values": [...] or None} -- values = what the recreate gave every entity of an emitted batch (-1 = left
+        unassigned).  A MoveKind.SCALAR_RUIN record's `a` indexes it."""
+        cnt, emitted = np.zeros(16, dtype=np.int32), np.zeros(16, dtype=np.int32)
+        ent, val = np.zeros((16, 8), dtype=np.int32), np.zeros((16, 8), dtype=np.int32)
+        check(self._L.sf_get_scalar_ruin_table(self._h, replica, ptr(cnt), ptr(ent), ptr(val), ptr(emitted)), self._h)
+        rows = []
+        for b in range(16):
+            k = int(cnt[b])
+            rows.append({"entities": [int(x) & 0xFFFFFFFF for x in ent[b, :k]], "emitted": bool(emitted[b]),
+                         "values": [int(x) for x in val[b, :k]] if emitted[b] else None})
+        return rows[:getattr(self, "_scalar_ruin_moves_per_step", 16)]
 
     def add_precedence_selector(self, descriptor_index, variable_index=0):
         """Critical-path precedence leaf (ListPrecedenceMoveSelector, heuristic/selector/list_precedence.rs:121-210) of a list class that
