@@ -923,7 +923,7 @@ int32_t sf_debug_tabu_script(sf_ctx* ctx, const sf_tabu_config* policy, int32_t 
                              int32_t n_records, const sf_tabu_record* records, uint64_t* out_accept, uint64_t* out_state);
 /* The second local-search type of the reference's configuration (solverforge-config/src/phase.rs:148-155): Variable Neighborhood Descent
  * (phase/localsearch/vnd/phase.rs:31-404).  The neighbourhoods are the context's declared leaves in declaration order (the order of the
- * sf_selector_add* calls), one leaf each, compiled with SelectionOrder::Original.  A step pulls the whole cursor of neighbourhood k and
+ * sf_selector_add* calls), one leaf each unless sf_vnd_set_neighborhoods groups them, compiled with SelectionOrder::Original.  A step pulls the whole cursor of neighbourhood k and
  * applies the first strictly best candidate that beats the current score strictly, then k = 0; a step that finds none applies nothing,
  * still counts as a step (step index and seed draw advance) and sets k += 1.  A replica is done at k == n: it runs no further step, in
  * this launch or a later one, until the next sf_phase_start.  sf_stats::moves_accepted and moves_applied count the applied pick only.
@@ -939,6 +939,27 @@ int32_t sf_solver_configure_vnd(sf_ctx* ctx);
 int32_t sf_get_vnd_state(sf_ctx* ctx, int32_t replica, int32_t* out_k, int32_t* out_n, int32_t* out_done, uint64_t* out_idle_steps);
 /* How many replicas are done: one read of 8 bytes per replica. */
 int32_t sf_vnd_done_count(sf_ctx* ctx, int32_t* out);
+/* MoveSelectorConfig::LimitedNeighborhood (solverforge-config/src/move_selector.rs:34-109; LimitedMoveCursor,
+ * heuristic/selector/decorator/limited.rs:14-94) around one leaf: per step the leaf's cursor answers at most selected_count_limit pulls and
+ * is never touched after that; the scheduler of the union sees a child that ran dry.  leaf_index = the zero-based order of the
+ * sf_selector_add* calls.  selected_count_limit >= 0 sets the limit (0 = the leaf yields nothing), -1 removes it, anything below is
+ * SF_ERR_INVALID, as is an unknown leaf; a limit that a 32-bit pull count cannot reach (>= 2^32 - 1) is stored as none.  May be called
+ * between launches and takes effect at the next launch.  A context with any limit runs in the generic engine whatever the model.
+ * SF_ERR_UNSUPPORTED at launch: a forced block, wave or scalar engine; a limit while the union holds a list ruin, scalar ruin or
+ * critical-path leaf.  sf_step_generate honours the limits. */
+int32_t sf_selector_limit(sf_ctx* ctx, int32_t leaf_index, int64_t selected_count_limit);
+/* LimitedNeighborhood around the root union: a step's cursor yields at most selected_count_limit pulls over all children, then the step
+ * ends exactly as it does when every child is exhausted.  Same value rules and refusals as sf_selector_limit.  Not used under Variable
+ * Neighborhood Descent, whose neighbourhoods carry their own limits. */
+int32_t sf_union_limit(sf_ctx* ctx, int64_t selected_count_limit);
+/* The neighbourhoods of Variable Neighborhood Descent as compositions (the reference compiles the composition nodes alike for both
+ * local-search types, runtime/compiler/graph.rs:216-218).  Neighbourhood h = the declared leaves first_leaf[h] .. first_leaf[h + 1] - 1
+ * (first_leaf[n_hoods + 1]: contiguous, non-empty, covering every leaf); a group of more than one leaf is a union with equal weights
+ * scheduled in union_order[h] (sf_union_order) over its own child count; hood_limit[h] (-1 = none) wraps the whole neighbourhood;
+ * sf_selector_limit applies inside a group.  n_hoods == 0 returns to one leaf each (the default; the arrays may be NULL).  k and n of
+ * sf_get_vnd_state count neighbourhoods; the leaf index of a traced record stays the global one.  SF_ERR_INVALID: a malformed table, a bad
+ * order or limit.  Takes effect at the next sf_phase_start. */
+int32_t sf_vnd_set_neighborhoods(sf_ctx* ctx, int32_t n_hoods, const int32_t* first_leaf, const int32_t* union_order, const int64_t* hood_limit);
 int32_t sf_solver_set_engine(sf_ctx* ctx, int32_t engine); /* sf_engine_kind; SF_ERR_UNSUPPORTED if it cannot run this model */
 int32_t sf_solver_get_engine(sf_ctx* ctx, int32_t* out_engine); /* the engine launches resolve to (after sf_initialize) */
 /* How the wave engine laid out its last fused launch (diagnostics; tests assert the path they mean to cover was taken):

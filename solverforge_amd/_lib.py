@@ -100,6 +100,7 @@ SYMBOLS = [
     "sf_solver_configure_tabu", "sf_get_tabu_state", "sf_debug_tabu_script",
     "sf_solver_configure_vnd", "sf_get_vnd_state", "sf_vnd_done_count",
     "sf_selector_add_scalar_ruin", "sf_get_scalar_ruin_table",
+    "sf_selector_limit", "sf_union_limit", "sf_vnd_set_neighborhoods",
     "sf_solver_set_engine", "sf_solver_get_engine", "sf_list_wave_layout", "sf_list_arith_flags", "sf_constraint_add_pair_join", "sf_constraint_add_uni_program", "sf_provider_declare", "sf_phase_start", "sf_solve_steps", "sf_solve_moves", "sf_solve_step_traced", "sf_get_stats", "sf_get_stats_sum", "sf_get_best_scores",
     "sf_profile_solve", "sf_download_scalar", "sf_download_list", "sf_portfolio_unique_id",
     "sf_portfolio_init", "sf_portfolio_allgather_best", "sf_portfolio_broadcast_best", "sf_portfolio_destroy", "sf_portfolio_migrate_local",
@@ -171,6 +172,9 @@ def load():
     L.sf_selector_add_ruin.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, C.c_char_p]
     L.sf_selector_add_scalar_ruin.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, C.c_char_p]
     L.sf_get_scalar_ruin_table.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.sf_selector_limit.argtypes = [vp, i32, i64]
+    L.sf_union_limit.argtypes = [vp, i64]
+    L.sf_vnd_set_neighborhoods.argtypes = [vp, i32, vp, vp, vp]
     L.sf_solver_configure.argtypes = [vp, C.POINTER(SolverConfigStruct)]
     L.sf_default_local_search_components.argtypes = [i32, i32, i32, i32, i32, u64, C.POINTER(SolverConfigStruct)]
     L.sf_solver_configure_default.argtypes = [vp, u64, i32, i32, C.POINTER(SolverConfigStruct)]

@@ -61,6 +61,7 @@ struct SelectorSpec {
     int moves_per_step = 10, max_source_len = 0, skip_empty = 0;  // ruin leaf (ListRuinMoveSelectorConfig)
     std::string variable_name;                                    // ruin leaf: scoped_seed hashes the variable name
     int value_limit = -1, recreate = 0;                           // scalar ruin leaf: value_candidate_limit (-1 = None), sf_recreate_heuristic
+    int64_t limit = -1;                                           // sf_selector_limit: LimitedNeighborhood around this leaf (-1 = none)
 };
 struct NearbyScalarSource {  // sf_selector_add_nearby_scalar: rows ranked by (distance, source order, candidate)
     bool present = false;
@@ -161,6 +162,14 @@ struct sf_ctx {
     uint64_t tabu_arena_cap = 0;
     bool vnd = false;   // sf_solver_configure_vnd: the local-search type is Variable Neighborhood Descent until the next sf_solver_configure
     int vnd_n = -1;     // neighbourhoods of the phase that was started under it (sf_api_vnd.inc)
+    // LimitedNeighborhood and the VND neighbourhood table (sf_api_limited.inc).  `hoods_cfg` is what sf_vnd_set_neighborhoods last set,
+    // `hoods` what the phase was started with; `vnd_leaves` = the leaves of that phase.
+    int64_t union_limit = -1;  // sf_union_limit (-1 = none)
+    struct HoodTable {
+        std::vector<int32_t> first, order;  // [n + 1], [n]
+        std::vector<int64_t> limit;         // [n], -1 = none
+    } hoods_cfg, hoods;
+    int vnd_leaves = -1;
     uint64_t* d_explicit = nullptr;
     int64_t n_explicit = 0;
     // trace buffers
@@ -1916,8 +1925,10 @@ static int ensure_plf(sf_ctx* ctx) {
 }
 // the `order` argument of the precedence kernels a host drives: 0 = the penalty's level comes first, 1 = the makespan's, 2 = one level
 static int prec_level_order(const sf_ctx* ctx) { return ctx->pm.hard_level < ctx->pm.mk_level ? 0 : (ctx->pm.hard_level > ctx->pm.mk_level ? 1 : 2); }
+#include "sf_api_limited.inc"  // LimitedNeighborhood around a leaf / the root union, VND neighbourhoods as compositions: the ABI, refusals, LimitParams
 static int launch_mixed(sf_ctx* ctx, SearchParams& p, int grid, bool trace) {
     GLeaves gl{};
+    for (int l = 0; l < GL; ++l) gl.lim.leaf[l] = SF_LIMIT_NONE;
     gl.list_desc = ctx->has_list_model ? ctx->list_desc : 0;
     gl.xown_level = ctx->xown_level, gl.xown_weight = ctx->xown_weight, gl.xown_tab = ctx->d_xown_tab;
     // default-policy declaration order: list rules first, then scalar change, scalar swap
@@ -2008,6 +2019,7 @@ static int launch_mixed(sf_ctx* ctx, SearchParams& p, int grid, bool trace) {
             }
             gl.min_size[gl.n] = s.min_size;
             gl.max_size[gl.n] = s.max_size;
+            gl.lim.leaf[gl.n] = limit_word(s.limit);
             gl.kind[gl.n++] = kind;
         }
     if (gl.n == 0) return fail(ctx, SF_ERR_INVALID, "no selector configured");
@@ -2020,7 +2032,8 @@ static int launch_mixed(sf_ctx* ctx, SearchParams& p, int grid, bool trace) {
     }
     const GenericKnobs knobs = generic_knobs();
     gl.plf.slow = knobs.plf_slow, gl.plf.force64 = knobs.plf_force64;
-    if (vnd && gl.n != ctx->vnd_n) return fail(ctx, SF_ERR_INVALID, "variable neighborhood descent: the leaves changed since sf_phase_start");
+    if (vnd && gl.n != ctx->vnd_leaves) return fail(ctx, SF_ERR_INVALID, "variable neighborhood descent: the leaves changed since sf_phase_start");
+    if (int rc = limited_fill(ctx, gl, vnd, trace)) return rc;
     gl.union_order = vnd ? SF_UNION_SEQUENTIAL : ctx->union_order >= 0 ? ctx->union_order : (gl.n > 1 ? SF_UNION_STRATIFIED_RANDOM : SF_UNION_SEQUENTIAL);
     gl.union_custom = !vnd && union_is_custom(ctx) && gl.n > 1 ? 1 : 0;
     for (int l = 0; l < GL; ++l) gl.weight[l] = 1;
@@ -2087,6 +2100,17 @@ static int launch_search(sf_ctx* ctx, SearchParams& p, int grid, bool trace) {
     if (p.acceptor == VND_KIND) {
         if (ctx->sp.acceptor != VND_KIND) return fail(ctx, SF_ERR_INVALID, "variable neighborhood descent: sf_phase_start after sf_solver_configure_vnd");
         if (const char* why = vnd_launch_refusal(ctx)) return fail(ctx, SF_ERR_UNSUPPORTED, why);
+        if (const char* why = limited_launch_refusal(ctx, true)) return fail(ctx, SF_ERR_UNSUPPORTED, why);
+        return launch_mixed(ctx, p, grid, true);
+    }
+    // LimitedNeighborhood around a leaf or the root union, and a neighbourhood grouping, live in the generic engine's TRACE
+    // instantiations too: such a context runs there whatever the model, with no replica traced unless the caller traces one
+    if (limited_any(ctx)) {
+        if (const char* why = limited_launch_refusal(ctx, false)) return fail(ctx, SF_ERR_UNSUPPORTED, why);
+        if (scalar_ruin_selector(ctx)) {
+            if (!ctx->d_sruin_rng) return fail(ctx, SF_ERR_INVALID, "scalar ruin leaf: sf_phase_start seeds its stream first");
+            if (const char* why = scalar_ruin_launch_refusal(ctx)) return fail(ctx, SF_ERR_UNSUPPORTED, why);
+        }
         return launch_mixed(ctx, p, grid, true);
     }
     // The scalar ruin-and-recreate leaf (sf_scalar_ruin.h) lives in the generic engine's TRACE instantiations: a union that holds it runs there

@@ -3,7 +3,8 @@
 // Included into sf_api.hip (same translation unit, same build flags as the rest of the library).
 
 // LocalSearchType::VariableNeighborhoodDescent (solverforge-config/src/phase.rs:148-155): the neighbourhoods are the context's declared
-// leaves in declaration order, one leaf each, compiled with SelectionOrder::Original (runtime/compiler/local_search.rs:55-89).  The
+// leaves in declaration order, one leaf each (or the groups of sf_vnd_set_neighborhoods, sf_api_limited.inc), compiled with
+// SelectionOrder::Original (runtime/compiler/local_search.rs:55-89).  The
 // acceptor, forager, random-ties, selection-order and union settings are ignored while it holds; sf_solver_configure (and
 // sf_solver_configure_default, which calls it) returns the context to acceptor-forager search.
 extern "C" int32_t sf_solver_configure_vnd(sf_ctx* ctx) {
@@ -26,7 +27,11 @@ static int vnd_neighbourhoods(const sf_ctx* ctx) {
 // sf_phase_start under the phase: zeros and n in every replica's row; the phase-start kernels set k and the done flag (vnd_phase_started).
 // `st` = the R rows about to be uploaded.
 static void vnd_phase_rows(sf_ctx* ctx, std::vector<uint64_t>& st) {
-    ctx->vnd_n = vnd_neighbourhoods(ctx);
+    // the neighbourhoods of the phase: one declared leaf each, or the groups sf_vnd_set_neighborhoods set (sf_api_limited.inc) -- k and n
+    // count neighbourhoods either way
+    ctx->hoods = ctx->hoods_cfg;
+    ctx->vnd_leaves = vnd_neighbourhoods(ctx);
+    ctx->vnd_n = ctx->hoods.first.empty() ? ctx->vnd_leaves : (int)ctx->hoods.order.size();
     for (int r = 0; r < ctx->R; ++r) {
         uint64_t* w = st.data() + (size_t)r * SA_WORDS;
         std::fill(w, w + SA_WORDS, (uint64_t)0);

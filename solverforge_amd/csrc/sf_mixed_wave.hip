@@ -88,6 +88,19 @@ __host__ __device__ inline bool has_scalar_ruin_leaf(const int32_t (&kind)[GL], 
     return has;
 }
 
+// LimitedNeighborhood (heuristic/selector/decorator/limited.rs:14-94) around a leaf or around the root union, and the neighbourhoods of
+// Variable Neighborhood Descent as compositions (the TRACE instantiations carry them).  A limit counts the pulls the wrapped
+// cursor answered in this step; SF_LIMIT_NONE = no limit.
+constexpr uint32_t SF_LIMIT_NONE = 0xFFFFFFFFu;
+struct LimitParams {
+    uint32_t leaf[GL];         // per leaf, in launch order
+    uint32_t root;             // the root union's (acceptor-forager search)
+    int32_t n_hoods;           // 0 = one leaf each
+    uint8_t hood_first[GL + 4];  // [n_hoods + 1] neighbourhood h = the leaves hood_first[h] .. hood_first[h + 1] - 1
+    uint8_t hood_order[GL];    // sf_union_order of a neighbourhood of more than one leaf
+    uint32_t hood_limit[GL];   // the limit around neighbourhood h
+};
+
 struct GLeaves {
     int32_t n;
     int32_t kind[GL];   // sf_selector_kind: 1 scalar change, 2 scalar swap, 4 list change, 8 list swap, 64 list reverse,
@@ -133,6 +146,7 @@ struct GLeaves {
     uint16_t* xown_tab;
     uint32_t* node_tab;      // [R][dim] node -> (list << 16 | position) in HBM: the FAST + ruin instantiation keeps it out of the LDS slice (12 replicas per CU)
     SRuinParams sruin;       // scalar ruin-and-recreate leaf (kind 32768): parameters, per-solve stream, trace table
+    LimitParams lim;         // leaf / root limits and the VND neighbourhood table (read by the TRACE instantiations only)
 };
 
 // u16 entries of RuinFast::slot: the slot table of sf_ruin.h (n_cap + V) and the arena of sf_ruin_v2.h, which never overflows at n_cap + 21
@@ -1385,11 +1399,36 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                 }
             }
         // union scheduler (vec_union.rs:190-365): StratifiedRandom with equal weights when > 1 leaf
-        const uint32_t u_off = nl > 1 ? ctx.random_index((uint32_t)nl, SALT_UNION_OFFSET) : 0u;
-        const uint32_t u_str = nl > 1 ? ctx.random_stride((uint32_t)nl, SALT_UNION_STRIDE) : 1u;
+        // The union this step's cursor schedules: children u_lo .. u_lo + u_n - 1.  The root union's are all the leaves; a VND step's are the
+        // leaves of neighbourhood k (one leaf, or a group of sf_vnd_set_neighborhoods), scheduled over ITS child count (vec_union.rs:119-124,
+        // 190-365: the seeded offset and stride are drawn over that union's n).  root_left = what is left of the limit around that union.
+        // (The untraced kernels keep the parent's expressions over `nl` word for word -- every `TRACE ? .. : ..` below is folded by the front
+        // end -- so that they stay instruction-identical: profiles/limited_isa.txt.)
+        [[maybe_unused]] uint32_t u_lo = 0, u_n = 1;
+        [[maybe_unused]] int u_ord_cfg = 0;
+        [[maybe_unused]] uint32_t root_left = SF_LIMIT_NONE;
+        if constexpr (TRACE) {
+            u_n = (uint32_t)nl, u_ord_cfg = FAST ? 4 : gl.union_order;
+            root_left = gl.lim.root;
+            if (acceptor == VND_KIND) {
+                u_lo = vnd_k, u_n = 1, root_left = SF_LIMIT_NONE;
+                if (gl.lim.n_hoods > 0) {
+#pragma unroll
+                    for (int h = 0; h < GL; ++h)  // (compile-time h: no dynamic indexing of the kernarg block)
+                        if ((uint32_t)h == vnd_k) {
+                            u_lo = gl.lim.hood_first[h], u_n = (uint32_t)gl.lim.hood_first[h + 1] - u_lo;
+                            u_ord_cfg = gl.lim.hood_order[h], root_left = gl.lim.hood_limit[h];
+                        }
+                }
+                u_lo = uni(u_lo), u_n = uni(u_n), u_ord_cfg = (int)uni((uint32_t)u_ord_cfg);
+            }
+            root_left = uni(root_left);
+        }
+        const uint32_t u_off = TRACE ? (u_n > 1 ? ctx.random_index(u_n, SALT_UNION_OFFSET) : 0u) : (nl > 1 ? ctx.random_index((uint32_t)nl, SALT_UNION_OFFSET) : 0u);
+        const uint32_t u_str = TRACE ? (u_n > 1 ? ctx.random_stride(u_n, SALT_UNION_STRIDE) : 1u) : (nl > 1 ? ctx.random_stride((uint32_t)nl, SALT_UNION_STRIDE) : 1u);
         int32_t live_weight = nl;  // total weight of the live children (running weights of the smooth weighted round-robin: leaf table)
         uint32_t u_cur = 0, u_draw = 0;  // RoundRobin cursor / Random draw counter of this step's cursor
-        const int u_ord = nl > 1 ? (FAST ? 4 : gl.union_order) : 0;
+        const int u_ord = TRACE ? (u_n > 1 ? u_ord_cfg : 0) : (nl > 1 ? (FAST ? 4 : gl.union_order) : 0);
         if (union_custom) {  // weighted children: a zero weight is an exhausted child from the start (vec_union.rs:214-218)
             live_weight = 0;
 #pragma unroll
@@ -1403,20 +1442,27 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
             }
             if (u_ord == 2) u_cur = u_off;  // RotatingRoundRobin starts at the seeded offset
         }
-        // Variable Neighborhood Descent opens the cursor of neighbourhood k alone (phase.rs:79-80): every other leaf is an exhausted child
-        // from the start, as a zero-weight one is.  The host hands over unit weights and no custom union, so the one live child weighs 1.
+        // Variable Neighborhood Descent opens the cursor of neighbourhood k alone (phase.rs:79-80): every leaf outside it is an exhausted child
+        // from the start, as a zero-weight one is.  The host hands over unit weights and no custom union, so every live child weighs 1.
+        // The round-robin cursors walk the global leaf indices: with the leaves outside the group exhausted that is the group's own cycle,
+        // started at the group's first child (RoundRobin) or at its seeded offset (RotatingRoundRobin).
         if constexpr (TRACE)
             if (acceptor == VND_KIND) {
 #pragma unroll
                 for (int l = 0; l < GL; ++l) {
-                    if (l >= nl || (uint32_t)l == vnd_k) continue;
+                    if (l >= nl || ((uint32_t)l >= u_lo && (uint32_t)l < u_lo + u_n)) continue;
                     exmask |= 1u << l;
                     lt.set(l, LeafTab::EX, 1);
                 }
-                live_weight = 1;
+                live_weight = (int32_t)u_n;
+                u_cur = u_ord == 2 ? u_lo + u_off : u_lo;
             }
-        uint64_t u_order = 0;  // rotated child order of this step, 4 bits per position (nl <= 16)
-        for (uint32_t pos = 0; pos < (uint32_t)nl; ++pos) u_order |= (uint64_t)((u_off + pos * u_str) % (uint32_t)nl) << (4u * pos);
+        uint64_t u_order = 0;  // rotated child order of this step, 4 bits per position (u_n <= nl <= 16)
+        if constexpr (TRACE) {
+            for (uint32_t pos = 0; pos < u_n; ++pos) u_order |= (uint64_t)(u_lo + (u_off + pos * u_str) % u_n) << (4u * pos);
+        } else {
+            for (uint32_t pos = 0; pos < (uint32_t)nl; ++pos) u_order |= (uint64_t)((u_off + pos * u_str) % (uint32_t)nl) << (4u * pos);
+        }
         u_order = uni64(u_order);
 
         PHS(0)
@@ -1443,6 +1489,18 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                 // (a generator call appends at most 64, the ring holds 128), so that the scoring stage below finds ~64 new entries of one kind at a time
                 const uint32_t fill_to = (pre_eval && lump_fill) ? (tl - hd_l < fill_thr ? 64u : 0u) : fill_thr;
                 if (pre_eval) lt.set(l, LeafTab::TAKEN, tl);  // (TAKEN is free between two replays) first entry the scoring stage has not seen
+                // LimitedMoveCursor around this leaf (limited.rs:14-94): the cursor answers `limit` pulls per step and never touches the inner
+                // cursor after that.  TAIL counts the candidates the leaf's cursor has answered since the step began (HEAD and TAIL restart at 0
+                // with every step), so the limit is a clamp on TAIL plus DONE: both scheduler paths below then see the child exactly as one
+                // that ran dry, a None on the pull after its last candidate.  (Ring entries written past the clamp are never read.)
+                [[maybe_unused]] uint32_t leaf_lim = SF_LIMIT_NONE;
+                if constexpr (TRACE) {
+#pragma unroll
+                    for (int q = 0; q < GL; ++q)  // (compile-time q: no dynamic indexing of the kernarg block)
+                        if (q == l) leaf_lim = gl.lim.leaf[q];
+                    leaf_lim = uni(leaf_lim);
+                    if (tl >= leaf_lim) g.done = 1;  // (a limit of 0 yields nothing)
+                }
                 while (!ex_l && !g.done && tl - hd_l < fill_to) {
                     st_sources += 1;
                     bool keep = false;
@@ -2261,6 +2319,8 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                         }
                     }
                     tl += (uint32_t)__popcll(km);
+                    if constexpr (TRACE)
+                        if (tl >= leaf_lim) tl = leaf_lim, g.done = 1;
                 }
                 lt.put_gen(l, g);
                 lt.set(l, LeafTab::TAIL, tl);
@@ -2300,13 +2360,25 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
             for (int l = 0; l < nl; ++l) lt.set(l, LeafTab::TAKEN, 0);
             uint32_t nvalid = 0;
             bool need_more = false;
+            // the limit around the union: a batch holds at most what is left of it, and a spent budget ends the step as exhausted children do
+            [[maybe_unused]] uint32_t batch_max = 64;
+            if constexpr (TRACE) {
+                if (root_left == 0) {
+                    done = 1;
+                    break;
+                }
+                batch_max = root_left < 64u ? root_left : 64u;
+            }
             {
                 int nlive = __popc(~exmask & ((1u << nl) - 1u));
                 // Fast path: with equal weights the smooth weighted round-robin is a plain cycle over the
                 // live children in rotated order whenever all their running weights are equal (true at the
                 // start of every step and after every whole cycle).  Lay out whole cycles directly; the
                 // pull-by-pull simulation below handles partial cycles, exhaustion and refills.
-                if (nl > 1 && nlive > 1 && !union_custom) {
+                // (a VND group under another order than StratifiedRandom has no custom root union, but is not a smooth round-robin either)
+                [[maybe_unused]] bool cycles_ok = true;
+                if constexpr (TRACE) cycles_ok = u_ord == 4;
+                if (nl > 1 && nlive > 1 && !union_custom && (!TRACE || cycles_ok)) {
                     // One cycle of the smooth weighted round-robin with equal weights pulls every live child once, in
                     // descending running weight (ties: rotated order), and leaves the weights as it found them -- provided
                     // max - min < live children (true with equal weights at the start of a step, and again a few pulls
@@ -2332,7 +2404,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                         if (ro_hit) {
                             r_order = ro_cache;
                         } else {
-                            for (uint32_t pi = 0; pi < (uint32_t)nl; ++pi) {      // rotated position pi holds leaf i
+                            for (uint32_t pi = 0; pi < (TRACE ? u_n : (uint32_t)nl); ++pi) {      // rotated position pi holds leaf i
                                 const uint32_t i = (uint32_t)(u_order >> (4u * pi)) & 15u;
                                 if (!((livem >> i) & 1u)) continue;
                                 if (wmax == wmin) {  // equal running weights (the steady state): the rotated order itself
@@ -2342,7 +2414,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                                 }
                                 const int32_t wi = __builtin_amdgcn_readlane(wc, (int)i);
                                 uint32_t rank = 0;
-                                for (uint32_t pj = 0; pj < (uint32_t)nl; ++pj) {
+                                for (uint32_t pj = 0; pj < (TRACE ? u_n : (uint32_t)nl); ++pj) {
                                     const uint32_t j = (uint32_t)(u_order >> (4u * pj)) & 15u;
                                     if (!((livem >> j) & 1u)) continue;
                                     const int32_t wj = __builtin_amdgcn_readlane(wc, (int)j);
@@ -2363,6 +2435,9 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                         const uint32_t cycles = upto / (uint32_t)nlive;  // whole cycles only: the running weights stay as they are
                         if (cycles > 0) {
                             nvalid = cycles * (uint32_t)nlive;
+                            // The limit around the union may keep a partial cycle here, which leaves TAKEN and the running weights wrong for
+                            // a next batch.  That is sound only because there is none: the budget is spent and the step ends with this batch.
+                            if constexpr (TRACE) nvalid = nvalid < batch_max ? nvalid : batch_max;
                             if (lane < nvalid) {
                                 my_leaf = leaf;
                                 my_idx = hd + cyc;
@@ -2383,7 +2458,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                     const uint32_t dn = isleaf ? lt.w[lane * 16 + LeafTab::DONE] : 1u;
                     uint32_t tk = 0;  // TAKEN was just cleared
                     uint32_t mypos = 0;
-                    for (uint32_t pos = 0; pos < (uint32_t)nl; ++pos)
+                    for (uint32_t pos = 0; pos < (TRACE ? u_n : (uint32_t)nl); ++pos)
                         if (((uint32_t)(u_order >> (4u * pos)) & 15u) == lane) mypos = pos;
                     int32_t wgt = 1;  // child weight (UnionWeighting); lane l = leaf l
                     if (union_custom) {
@@ -2392,7 +2467,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                         for (int l = 0; l < GL; ++l)
                             if (lane == (uint32_t)l) wgt = gl.weight[l];
                     }
-                    while (nvalid < 64 && nlive > 0) {
+                    while (nvalid < (TRACE ? batch_max : 64u) && nlive > 0) {
                         uint32_t sel = 0;
                         const bool live_l = isleaf && !((exmask >> lane) & 1u);
                         const uint32_t cur_before = u_cur;
@@ -2802,6 +2877,11 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                 // every laid-out pull is consumed unless the forager cut the step (which ends it)
                 for (int l = 0; l < nl; ++l) lt.set(l, LeafTab::HEAD, lt.get(l, LeafTab::HEAD) + lt.get(l, LeafTab::TAKEN));
                 if (forager_quits(forager, (uint32_t)p.limit, accepted, has_best, improving_pick)) done = 1;
+                if constexpr (TRACE)
+                    if (root_left != SF_LIMIT_NONE) {  // (nvalid <= root_left: the batch was cut to it)
+                        root_left -= nvalid;
+                        if (root_left == 0) done = 1;
+                    }
             }
             PHS(6)
         }

@@ -713,6 +713,42 @@ class GpuScoreDirector:
         k == n.  Runs in the generic engine whatever the model; ruin and precedence leaves and forced engines are refused at launch."""
         check(self._L.sf_solver_configure_vnd(self._h), self._h)
 
+    def limit_selector(self, leaf, selected_count_limit):
+        """LimitedNeighborhood around one leaf (limited.rs:14-94): the leaf's cursor answers at most selected_count_limit pulls per step
+        (0 = none at all; None or -1 removes the limit).  leaf = the zero-based order of the add_*selector calls.  May be called between
+        launches; runs in the generic engine whatever the model."""
+        check(self._L.sf_selector_limit(self._h, int(leaf), -1 if selected_count_limit is None else int(selected_count_limit)), self._h)
+
+    def limit_union(self, selected_count_limit):
+        """LimitedNeighborhood around the root union: a step's cursor yields at most selected_count_limit pulls over all children, then the
+        step ends as it does when every child is exhausted (None or -1 removes the limit)."""
+        check(self._L.sf_union_limit(self._h, -1 if selected_count_limit is None else int(selected_count_limit)), self._h)
+
+    def set_vnd_neighborhoods(self, groups, union_orders=None, limits=None):
+        """The neighbourhoods of Variable Neighborhood Descent as compositions: groups = a list of leaf counts, or of ranges / sequences of
+        consecutive leaf indices, that covers the declared leaves in order; a group of several leaves is a union with equal weights under
+        union_orders[h] (default Sequential, scheduled over its own child count), limits[h] (None = no limit) wraps the whole
+        neighbourhood.  An empty list returns to one leaf each.  Takes effect at the next phase_start."""
+        first = [0]
+        for g in groups:
+            if isinstance(g, (int, np.integer)):
+                first.append(first[-1] + int(g))
+            else:
+                g = list(g)
+                if g != list(range(first[-1], first[-1] + len(g))):
+                    raise ValueError("neighbourhood groups must be consecutive leaf indices in declaration order")
+                first.append(first[-1] + len(g))
+        n = len(first) - 1
+        if n == 0:
+            check(self._L.sf_vnd_set_neighborhoods(self._h, 0, None, None, None), self._h)
+            return
+        orders = [0] * n if union_orders is None else [int(o) for o in union_orders]
+        lims = [-1] * n if limits is None else [-1 if v is None else int(v) for v in limits]
+        if len(orders) != n or len(lims) != n:
+            raise ValueError("one union order and one limit per neighbourhood")
+        f, o, l = np.asarray(first, dtype=np.int32), np.asarray(orders, dtype=np.int32), np.asarray(lims, dtype=np.int64)
+        check(self._L.sf_vnd_set_neighborhoods(self._h, n, ptr(f), ptr(o), ptr(l)), self._h)
+
     def vnd_state(self, replica=0):
         """{"k": neighbourhood of the next step, "n": neighbourhoods, "done": k == n, "idle_steps": steps that found nothing} of one replica."""
         k, n, done, idle = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_uint64(0)
