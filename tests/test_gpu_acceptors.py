@@ -9,7 +9,9 @@ host-driven provider step.  The oracle cannot run these acceptors, so the tests 
    mirror's, an oracle model that follows by apply_move confirms the traced scores and doability.  The events that tell the rules apart
    (EVENTS) must all occur PER SITE, not per run: the water-level events belong to GreatDeluge and the count events to StepCounting, so no
    single run can hold all six; the three runs of a site (TRACE) together must, the GreatDeluge run holding its two and the FirstAccepted
-   StepCounting run its two;
+   StepCounting run its two.  These runs follow replica 0; the two FirstAccepted runs are traced at replicas 1 and 2 as well, against a
+   mirror and an oracle model of their own (fused == traced cannot see a wrong state-row stride: both kernels share the arithmetic);
+   tests/test_gpu_acceptor_state_at_size.py does the same at launches of several residencies;
 3. the same configuration fused (two launches; two budgeted launches) ends in the state the traced run reached;
 4. validation.
 
@@ -39,6 +41,14 @@ TRACE = {"gd_first": (GD, 0.04, 1, 0), "sc_first": (SC, 3, 1, 0), "sc_best": (SC
 EVENTS = ("accepted_through_water_only", "refused_below_water", "equal_to_cur_refused", "step_applied_nothing", "since_reached_limit", "since_reset_afterwards")
 
 _memo = {}
+
+
+class _Events(dict):
+    """event -> the first step that showed it; `add` as a set's, so that a run can say how many steps its events needed."""
+    step = 0
+
+    def add(self, event):
+        self.setdefault(event, self.step)
 
 
 def _build(site, n_replicas=R):
@@ -86,11 +96,11 @@ def _state(d, site, r):
     return d.working_values(0, 0, replica=r).tolist() if site == "scalar" else d.working_lists(0, r)
 
 
-def _snapshot(d, site, with_acceptor):
+def _snapshot(d, site, with_acceptor, replicas=range(R)):
     """Per replica: (score, best score, working state, the seven counters, acceptor state)."""
     scores, best = d.calculate_score(), d.best_scores()
     out = []
-    for r in range(R):
+    for r in replicas:
         st = d.stats(r)
         ax = d.acceptor_state(r) if with_acceptor else None
         out.append((scores[r].tolist(), best[r].tolist(), _state(d, site, r), [st[k] for k in COUNTERS],
@@ -182,22 +192,25 @@ def test_equivalence_provider_step(oracle, which):
 
 
 # ---- 2. traced replay against the mirror ---------------------------------------------------------------------------------------------
-def traced_run(oracle, site, acceptor, param, forager, limit, steps=STEPS):
-    """Replica 0 step by step through sf_solve_step_traced (the launch moves every replica one step).  Returns (events seen, the
-    snapshot of all replicas after the run)."""
-    d = _build(site)
-    order, bits, seed = _site_cfg(oracle, site)
-    _configure(d, acceptor, param, forager, limit, order, seed)
-    o = _oracle_model(oracle, site)  # follows replica 0 by apply_move: its own search code plays no part
+def _acceptor_tuple(d, r):
+    level, incr, since = d.acceptor_state(r)
+    return tuple(level.tolist()), tuple(incr.tolist()), since
+
+
+def trace_replica(oracle, d, site, acceptor, param, replica, steps):
+    """One replica of a context at the start of a phase under GreatDeluge / StepCounting, step by step through sf_solve_step_traced (the
+    launch moves every replica one step).  The oracle model follows that replica by apply_move from the site's start state: its own
+    search code plays no part.  Returns {event: the first step that showed it}."""
+    o = _oracle_model(oracle, site)
     mirror = am.GreatDeluge(param) if acceptor == GD else am.StepCounting(param)
     cur = tuple(int(x) for x in o.score()[:2])
-    assert tuple(d.calculate_score()[0].tolist()) == cur
+    assert tuple(d.calculate_score()[replica].tolist()) == cur
     mirror.phase_started(cur)
-    events, reached = set(), False
+    events, reached = _Events(), False
     for step in range(steps):
-        level, incr, since = d.acceptor_state(0)
-        assert (tuple(level.tolist()), tuple(incr.tolist()), since) == mirror.state(), step
-        gm, gs, gf, gap, gmv = d.solve_step_traced(replica=0, cap=1 << 17)
+        events.step = step
+        assert _acceptor_tuple(d, replica) == mirror.state(), (replica, step)
+        gm, gs, gf, gap, gmv = d.solve_step_traced(replica=replica, cap=1 << 17)
         os_, od = o.evaluate_moves(gm)
         doable = (gf & 1) != 0
         assert (doable == (od != 0)).all(), step
@@ -223,7 +236,7 @@ def traced_run(oracle, site, acceptor, param, forager, limit, steps=STEPS):
             events.add("step_applied_nothing")
             assert not (gf & 2).any()
         cur = tuple(int(x) for x in o.score()[:2])
-        assert tuple(d.calculate_score()[0].tolist()) == cur, step
+        assert tuple(d.calculate_score()[replica].tolist()) == cur, (replica, step)
         mirror.step_ended(cur)
         if acceptor == SC:
             if mirror.since >= mirror.limit:
@@ -231,16 +244,27 @@ def traced_run(oracle, site, acceptor, param, forager, limit, steps=STEPS):
                 reached = True
             if reached and mirror.since == 0:
                 events.add("since_reset_afterwards")
-    level, incr, since = d.acceptor_state(0)
-    assert (tuple(level.tolist()), tuple(incr.tolist()), since) == mirror.state()
-    assert _state(d, site, 0) == (o.get_vars(0, 0).tolist() if site == "scalar" else o.get_lists(0))
-    return events, _snapshot(d, site, True)
+    assert _acceptor_tuple(d, replica) == mirror.state(), replica
+    assert _state(d, site, replica) == (o.get_vars(0, 0).tolist() if site == "scalar" else o.get_lists(0)), replica
+    return events
 
 
-def _traced(oracle, site, run):
-    key = ("traced", site, run)
+def traced_run(oracle, site, acceptor, param, forager, limit, steps=STEPS, replica=0, n_replicas=R, seed=None, snapshot_of=None):
+    """Replica `replica` of a fresh context of n_replicas (replica r runs seed + r; default: the site's seed) through trace_replica.
+    Returns (events seen, the snapshot of the replicas snapshot_of -- default: all of them -- after the run)."""
+    d = _build(site, n_replicas=n_replicas)
+    order, _, site_seed = _site_cfg(oracle, site)
+    _configure(d, acceptor, param, forager, limit, order, site_seed if seed is None else seed)
+    events = trace_replica(oracle, d, site, acceptor, param, replica, steps)
+    snap = _snapshot(d, site, True, range(n_replicas) if snapshot_of is None else snapshot_of)
+    d.close()
+    return set(events), snap
+
+
+def _traced(oracle, site, run, replica=0):
+    key = ("traced", site, run, replica)
     if key not in _memo:
-        _memo[key] = traced_run(oracle, site, *TRACE[run])
+        _memo[key] = traced_run(oracle, site, *TRACE[run], replica=replica)
     return _memo[key]
 
 
@@ -250,6 +274,17 @@ def test_traced_replay_matches_the_mirror(oracle, site):
     assert not [e for e in EVENTS if e not in seen], sorted(seen)
     assert {"accepted_through_water_only", "refused_below_water"} <= _traced(oracle, site, "gd_first")[0]
     assert {"since_reached_limit", "since_reset_afterwards"} <= _traced(oracle, site, "sc_first")[0]
+
+
+@pytest.mark.parametrize("replica", [1, 2])
+@pytest.mark.parametrize("run", ["gd_first", "sc_first"])
+@pytest.mark.parametrize("site", SITES)
+def test_traced_replay_of_replicas_1_and_2(oracle, site, run, replica):
+    """The fused and the traced kernel reach a replica's acceptor-state row by the same arithmetic, so fused == traced says nothing about
+    a wrong stride or an aliased row.  Here the mirror and the oracle model follow replica 1 and replica 2; the launch moves every
+    replica whichever one is traced, so the run ends in the snapshot of the run that traced replica 0."""
+    _, snap = _traced(oracle, site, run, replica)
+    assert snap == _traced(oracle, site, run)[1]
 
 
 # ---- 3. fused == traced ---------------------------------------------------------------------------------------------------------------

@@ -7,7 +7,8 @@ dispatched into LDS and wave slots that earlier ones have left, and the launch e
 block engine (one 1,024-thread workgroup per replica, at most two per CU) runs R = 2 * 2 * CUs + 5.  The CU count is read from the device.
 
 Replica r is a function of random_seed + r and nothing else (step seeds, the annealing stream and the ruin stream all follow that rule),
-so every case checks, after 20 to 40 steps in two launches (SimulatedAnnealing: 300, so that its calibration completes):
+so every case checks, after 20 to 60 steps in two launches (SimulatedAnnealing on the scalar engine: 300, so that its calibration
+completes; the list engines run SimulatedAnnealing and every site but the block engine DiversifiedLateAcceptance too):
 
   1. a sample of replicas against the CPU oracle configured with random_seed + r: lists / values, score, best score, counters (and
      temperatures bit for bit under SimulatedAnnealing).  The sample always holds 0, 1, 3, 4, 5, 63, 64, R - 1, R - 2, R - 5 and both sides of
@@ -41,7 +42,8 @@ SEED = 7_000  # replica r of context A runs random_seed SEED + r
 SHIFT = 5     # context B: SEED + SHIFT
 WAVES_PER_CU = 32  # the most wavefronts a CU holds
 BLOCKS_PER_CU = 2  # 1,024-thread workgroups per CU
-SA = 3
+SA, DLA = 3, 4
+GENERIC_THREE = ("nearby_change", "nearby_swap", "list_reverse")  # a third leaf takes a list model to the generic engine
 
 
 @functools.lru_cache(maxsize=None)
@@ -84,14 +86,33 @@ def _rows_differ(a, b):
 
 
 # ---- the cases: a device context and an oracle of one configuration -----------------------------------------------------------------
+def _oracle_acceptor(acceptor):
+    """The oracle takes SimulatedAnnealing and DiversifiedLateAcceptance as LateAcceptance plus a configure call of their own."""
+    return 1 if acceptor in (SA, DLA) else acceptor
+
+
+def _configure_acceptor(case, d, seed):
+    if case.acceptor == SA:
+        d.configure_annealing(mode=2, calibration_sample_size=case.sample_size, seed=seed)
+    if case.acceptor == DLA:
+        d.configure_diversified(case.tolerance)
+
+
+def _configure_oracle_acceptor(case, o, seed):
+    if case.acceptor == SA:
+        o.configure_annealing(mode=2, sample_size=case.sample_size, seed=seed)
+    if case.acceptor == DLA:
+        o.configure_diversified(case.la, case.tolerance)
+
+
 class _Cvrp:
     levels = 2
-    anneal = False
 
     def __init__(self, problem, leaves, engine=None, acceptor=1, forager=0, la=24, limit=64, ruin=(2, 5, 10), steps=(20, 20), n_sample=48,
-                 env=(), path=None, block=False):
+                 env=(), path=None, block=False, sample_size=24, tolerance=0.02):
         self.p, self.leaves, self.engine, self.acceptor, self.forager, self.la, self.limit, self.ruin = problem, leaves, engine, acceptor, forager, la, limit, ruin
         self.steps, self.n_sample, self.env, self.path, self.block = steps, n_sample, dict(env), path, block
+        self.sample_size, self.tolerance, self.anneal = sample_size, tolerance, acceptor == SA
 
     def device(self, R, seed):
         import solverforge_amd as sfa
@@ -103,16 +124,18 @@ class _Cvrp:
             d.set_engine(self.engine)
         d.configure(sfa.SolverConfig(acceptor=self.acceptor, late_acceptance_size=self.la, forager=self.forager, accepted_count_limit=self.limit,
                                      random_seed=seed))
+        _configure_acceptor(self, d, seed)
         return d
 
     def cpu(self, oracle, seed):
         p = self.p() if callable(self.p) else self.p
         self.p = p
         o = oracle.Model.cvrp(p["capacity"], p["depot"], p["demands"], p["matrix"], p["customers"], p["routes"])
-        o.configure(acceptor=self.acceptor, la_size=self.la, forager=self.forager, limit=self.limit, leaves=sum(LEAF_BITS[x] for x in self.leaves),
+        o.configure(acceptor=_oracle_acceptor(self.acceptor), la_size=self.la, forager=self.forager, limit=self.limit, leaves=sum(LEAF_BITS[x] for x in self.leaves),
                     random_seed=seed, max_nearby=MAXN)
         if "ruin" in self.leaves:
             o.set_ruin(self.ruin[0], self.ruin[1], self.ruin[2], variable_name="visits")
+        _configure_oracle_acceptor(self, o, seed)
         return o
 
     def device_state(self, d, r):
@@ -127,8 +150,9 @@ class _Graph:
     block = False
     env = {}
 
-    def __init__(self, acceptor, la=20, limit=64, sample_size=24, steps=(20, 20), n_sample=48):
+    def __init__(self, acceptor, la=20, limit=64, sample_size=24, steps=(20, 20), n_sample=48, forager=0, tolerance=0.02):
         self.acceptor, self.la, self.limit, self.sample_size, self.steps, self.n_sample = acceptor, la, limit, sample_size, steps, n_sample
+        self.forager, self.tolerance = forager, tolerance
         self.anneal = acceptor == SA
         self.g = None
 
@@ -145,17 +169,17 @@ class _Graph:
         import solverforge_amd as sfa
 
         d = sfa.build_graph_coloring(self._graph(), n_replicas=R)
-        d.configure(sfa.SolverConfig(acceptor=self.acceptor, late_acceptance_size=self.la, forager=0, accepted_count_limit=self.limit, random_seed=seed))
-        if self.anneal:
-            d.configure_annealing(mode=2, calibration_sample_size=self.sample_size, seed=seed)
+        d.configure(sfa.SolverConfig(acceptor=self.acceptor, late_acceptance_size=self.la, forager=self.forager, accepted_count_limit=self.limit,
+                                     random_seed=seed))
+        _configure_acceptor(self, d, seed)
         return d
 
     def cpu(self, oracle, seed):
         g = self._graph()
         o = oracle.Model.graph_coloring(g["n_colors"], g["adj_off"], g["adj"], g["colors"])
-        o.configure(acceptor=1, la_size=self.la, forager=0, limit=self.limit, leaves=oracle.LEAF_SCALAR_CHANGE | oracle.LEAF_SCALAR_SWAP, random_seed=seed)
-        if self.anneal:
-            o.configure_annealing(mode=2, sample_size=self.sample_size, seed=seed)
+        o.configure(acceptor=_oracle_acceptor(self.acceptor), la_size=self.la, forager=self.forager, limit=self.limit,
+                    leaves=oracle.LEAF_SCALAR_CHANGE | oracle.LEAF_SCALAR_SWAP, random_seed=seed)
+        _configure_oracle_acceptor(self, o, seed)
         return o
 
     def device_state(self, d, r):
@@ -276,6 +300,19 @@ CASES = {
     "scalar_annealing": lambda: _Graph(acceptor=SA, limit=1, steps=(150, 150)),
     # block engine (engine 1)
     "block_two_leaf": lambda: _Cvrp(_small_cvrp, NEARBY, engine=1, block=True, path=_block_path),
+    # SimulatedAnnealing on the list engines, fused: the per-replica temperature row and annealing stream.  On the oracle, calibration over
+    # 128 samples under AcceptedCount(8) completes after 4 to 14 steps at the sampled seeds of a 256-CU and of a 304-CU device: far inside
+    # the 60 steps (the test asserts it for its own sample), and for some replicas behind the first launch of 10, which then writes a
+    # half-filled calibration back
+    "wave_annealing": lambda: _Cvrp(_small_cvrp, NEARBY, engine=2, acceptor=SA, limit=8, sample_size=128, steps=(10, 50), n_sample=32,
+                                    path=_wave_mode(lambda mode, renum: mode == 0)),
+    "generic_annealing": lambda: _Cvrp(_small_cvrp, GENERIC_THREE, acceptor=SA, limit=8, sample_size=128, steps=(10, 50), n_sample=32, path=_generic(fast=False, ruin=0)),
+    "block_annealing": lambda: _Cvrp(_small_cvrp, NEARBY, engine=1, acceptor=SA, limit=8, sample_size=128, steps=(10, 50), n_sample=32, block=True, path=_block_path),
+    # DiversifiedLateAcceptance (the block engine refuses it): the per-replica history and its late-score bookkeeping
+    "scalar_diversified": lambda: _Graph(acceptor=DLA, la=5, limit=8, n_sample=32),
+    "wave_diversified": lambda: _Cvrp(_small_cvrp, NEARBY, engine=2, acceptor=DLA, la=5, limit=8, n_sample=32,
+                                      path=_wave_mode(lambda mode, renum: mode == 0)),
+    "generic_diversified": lambda: _Cvrp(_small_cvrp, GENERIC_THREE, acceptor=DLA, la=5, limit=8, n_sample=24, path=_generic(fast=False, ruin=0)),
 }
 
 

@@ -12,7 +12,10 @@ tests/test_tabu_mirror.py) and on what the oracle can still confirm:
 
 Models: a colouring of 70 nodes with 4 colours (past one 64-lane chunk; unassigned allowed, so `to = None` changes occur) and the
 36-customer grid CVRP of tests/test_gpu_step_protocol.py (wave and generic sites); a mixed job shop of 12 operations on 3 machines (scalar
-class + list class: an operation index and an equal machine index are different tokens); 3 replicas with seeds s + r (a wrong arena offset shows in replica 2), 36 steps."""
+class + list class: an operation index and an equal machine index are different tokens); 3 replicas with seeds s + r, 36 steps.  The
+traced runs follow replica 0; the policy with all four memories is traced at replicas 1 and 2 as well, at every site, against a mirror
+and an oracle model of their own (a wrong arena offset or row stride shows there: fused == traced cannot see it, both kernels share
+the address arithmetic).  tests/test_gpu_acceptor_state_at_size.py does the same at launches of several residencies."""
 import pytest
 
 import tabu_mirror as tm
@@ -93,6 +96,14 @@ EVENTS = {"scalar": COMMON_EVENTS + ("to_none_refused_by_value",), "wave": COMMO
 _memo = {}
 
 
+class _Events(dict):
+    """event -> the first step that showed it; `add` as a set's, so that a run can say how many steps its events needed."""
+    step = 0
+
+    def add(self, event):
+        self.setdefault(event, self.step)
+
+
 def _problem():
     return _graph(n=70, e=170, k=4, seed=11)
 
@@ -115,15 +126,17 @@ def _mixed_problem():
     return _jobshop(n_jobs=MIXED_JOBS, n_machines=MIXED_MACHINES, seed=2)
 
 
-def _oracle_model(oracle, site):
+def _oracle_model(oracle, site, state=None):
+    """The oracle Model of a site, from its start state or from a replica's working state (the pair _state returns)."""
+    vals, lists = state if state is not None else (None, None)
     if site == "scalar":
         g = _problem()
-        return oracle.Model.graph_coloring(g["n_colors"], g["adj_off"], g["adj"], g["colors"])
+        return oracle.Model.graph_coloring(g["n_colors"], g["adj_off"], g["adj"], g["colors"] if vals is None else vals)
     if site == "mixed":
         p = _mixed_problem()
-        return oracle.Model.jobshop(p["job"], p["machine_idx"], p["sequences"], bendable=False)
+        return oracle.Model.jobshop(p["job"], p["machine_idx"] if vals is None else vals, p["sequences"] if lists is None else lists, bendable=False)
     p = _grid_cvrp()
-    return oracle.Model.cvrp(p["capacity"], p["depot"], p["demands"], p["matrix"], p["customers"], p["routes"])
+    return oracle.Model.cvrp(p["capacity"], p["depot"], p["demands"], p["matrix"], p["customers"], p["routes"] if lists is None else lists)
 
 
 def _state(d, site, r):
@@ -139,12 +152,12 @@ def _oracle_state(o, site):
     return vals, lists
 
 
-def _configure(d, policy, forager, limit, acceptor=TABU):
+def _configure(d, policy, forager, limit, acceptor=TABU, seed=SEED):
     import solverforge_amd as sfa
 
     d.configure_tabu(*policy)  # before the kind is named: sf_solver_configure takes kind 7 only once its policy was set
     d.configure(sfa.SolverConfig(acceptor=acceptor, late_acceptance_size=5, forager=forager, accepted_count_limit=limit, random_ties=True,
-                                 selection_order=ORDER_RANDOM, random_seed=SEED))
+                                 selection_order=ORDER_RANDOM, random_seed=seed))
     d.calculate_score()
     d.phase_start()
 
@@ -154,11 +167,11 @@ def _tabu_tuple(d, r):
     return (tuple(st["best"].tolist()) + (0, 0), tuple(st["pushes"]), st["entity"], st["value"], st["moves"], st["undo"])
 
 
-def _snapshot(d, site):
+def _snapshot(d, site, replicas=range(R)):
     """Per replica: (score, best score, working state, the seven counters, tabu state)."""
     scores, best = d.calculate_score(), d.best_scores()
     out = []
-    for r in range(R):
+    for r in replicas:
         st = d.stats(r)
         out.append((scores[r].tolist(), best[r].tolist(), _state(d, site, r), [st[k] for k in COUNTERS], _tabu_tuple(d, r)))
     assert (d.fresh_score() == scores).all()
@@ -181,22 +194,25 @@ def _signature(site, move, state):
     return tm.list_swap_signature(LIST_SCOPE[site], a, i, int(lists[a][i]), b, j, int(lists[b][j]))
 
 
-def traced_run(oracle, site, policy, forager, limit, leaves):
-    """Replica 0 step by step through sf_solve_step_traced (the launch moves every replica one step).  Returns (events seen, the snapshot
-    of all replicas after the run)."""
-    d = _build(site, leaves=leaves[site])
-    _configure(d, policy, forager, limit)
-    o = _oracle_model(oracle, site)  # follows replica 0 by apply_move: its own search plays no part
+def trace_replica(oracle, d, site, policy, replica, steps, o=None):
+    """One replica of a context at the start of a phase under TabuSearch, step by step through sf_solve_step_traced (the launch moves
+    every replica one step).  o: the oracle model of that replica's working state (default: the site's start state); it follows the
+    replica by apply_move, its own search plays no part.  The mirror starts fresh, as the phase does.  Returns {event: the first step
+    that showed it}."""
+    if o is None:
+        o = _oracle_model(oracle, site)
     packer = PACKER[site]
     mirror = tm.TabuSearch(policy)
     cur = tuple(int(x) for x in o.score()[:2])
-    assert tuple(d.calculate_score()[0].tolist()) == cur
+    assert tuple(d.calculate_score()[replica].tolist()) == cur
+    assert _state(d, site, replica) == _oracle_state(o, site)
     mirror.phase_started(cur)
-    events, refused_ids = set(), set()
-    for step in range(STEPS):
-        assert _tabu_tuple(d, 0) == tm.packed_state(mirror, packer), step
+    events, refused_ids = _Events(), set()
+    for step in range(steps):
+        events.step = step
+        assert _tabu_tuple(d, replica) == tm.packed_state(mirror, packer), (replica, step)
         vals = _oracle_state(o, site)
-        gm, gs, gf, gap, gmv = d.solve_step_traced(replica=0, cap=1 << 15)
+        gm, gs, gf, gap, gmv = d.solve_step_traced(replica=replica, cap=1 << 15)
         os_, od = o.evaluate_moves(gm)
         doable = (gf & 1) != 0
         assert (doable == (od != 0)).all(), step
@@ -235,17 +251,28 @@ def traced_run(oracle, site, policy, forager, limit, leaves):
             events.add("step_applied_nothing")
             assert not (gf & 2).any()
         cur = tuple(int(x) for x in o.score()[:2])
-        assert tuple(d.calculate_score()[0].tolist()) == cur, step
+        assert tuple(d.calculate_score()[replica].tolist()) == cur, (replica, step)
         mirror.step_ended(cur, applied_sig)
-    assert _tabu_tuple(d, 0) == tm.packed_state(mirror, packer)
-    assert _state(d, site, 0) == _oracle_state(o, site)
-    return events, _snapshot(d, site)
+    assert _tabu_tuple(d, replica) == tm.packed_state(mirror, packer), replica
+    assert _state(d, site, replica) == _oracle_state(o, site), replica
+    return events
 
 
-def _traced(oracle, site, name):
-    if (site, name) not in _memo:
-        _memo[(site, name)] = traced_run(oracle, site, *SITE_CONFIGS[site][name])
-    return _memo[(site, name)]
+def traced_run(oracle, site, policy, forager, limit, leaves, replica=0, n_replicas=R, seed=SEED, steps=STEPS, snapshot_of=None):
+    """Replica `replica` of a fresh context of n_replicas (replica r runs seed + r) through trace_replica.  Returns (events seen, the
+    snapshot of the replicas snapshot_of -- default: all of them -- after the run)."""
+    d = _build(site, n_replicas=n_replicas, leaves=leaves[site])
+    _configure(d, policy, forager, limit, seed=seed)
+    events = trace_replica(oracle, d, site, policy, replica, steps)
+    snap = _snapshot(d, site, range(n_replicas) if snapshot_of is None else snapshot_of)
+    d.close()
+    return set(events), snap
+
+
+def _traced(oracle, site, name, replica=0):
+    if (site, name, replica) not in _memo:
+        _memo[(site, name, replica)] = traced_run(oracle, site, *SITE_CONFIGS[site][name], replica=replica)
+    return _memo[(site, name, replica)]
 
 
 @pytest.mark.parametrize("site,name", CASES)
@@ -258,6 +285,17 @@ def test_traced_replay_matches_the_mirror(oracle, site, name):
     if name == "saturated":
         assert "step_applied_nothing" in events, sorted(events)
     assert len({str(s[2]) for s in snap}) == R  # replicas with seeds s + r differ from one another
+
+
+@pytest.mark.parametrize("replica", [1, 2])
+@pytest.mark.parametrize("site", SITES)
+def test_traced_replay_of_replicas_1_and_2(oracle, site, replica):
+    """The fused and the traced kernel reach a replica's tabu row and arena by the same arithmetic, so fused == traced says nothing about
+    a wrong stride or a stamp table that spills into the next replica's ring.  Here the mirror and the oracle model follow replica 1
+    and replica 2 of the policy with all four memories; the launch moves every replica whichever one is traced, so the run ends in
+    the snapshot of the run that traced replica 0."""
+    _, snap = _traced(oracle, site, "all_four", replica)
+    assert snap == _traced(oracle, site, "all_four")[1]
 
 
 @pytest.mark.parametrize("site", SITES)

@@ -10,12 +10,15 @@ oracle models:
 2. fused runs -- one launch of more steps than any replica needs, two launches, two budgeted launches, solve_vnd -- end where the traced
    runs did: working state, scores, best scores, the seven counters (the step count is the step index), vnd_state; a further launch
    changes nothing; the final state is a local optimum of every neighbourhood by the oracle;
-3. the way back to acceptor-forager search, and every refusal with its message."""
+3. the way back to acceptor-forager search, and every refusal with its message;
+4. two scripts at a launch of several residencies: the done count after launches that end some descents and not all, and a sample of
+   replicas (both sides of every residency boundary, the last ones) against mirrors run to done."""
 import numpy as np
 import pytest
 
 import vnd_cases as vc
 import vnd_mirror as vm
+from test_gpu_large_launch import _launch_size, _rows_differ, _sample
 from test_gpu_step_protocol import _decide_candidates
 
 pytestmark = pytest.mark.gpu
@@ -39,9 +42,9 @@ def _la_config(seed):
                             random_seed=seed)
 
 
-def _start(name):
+def _start(name, n_replicas=R):
     """The director of a script after the diverging search, at the start of a phase under VND."""
-    d = vc.device_model(name, R)
+    d = vc.device_model(name, n_replicas)
     d.configure(_la_config(SEEDS[name]))
     d.calculate_score()
     d.phase_start()
@@ -157,6 +160,58 @@ def test_solve_vnd_ends_in_a_local_optimum(oracle, name):
     for r in range(R):
         values, lists = vc.device_state(d, name, r)
         assert vm.is_local_optimum(vc.oracle_model(oracle, name, values, lists), vc.leaf_bits(name))
+
+
+# steps of the second solve_vnd call of test_vnd_at_size: with the 3 before them they end some descents and not all (on the oracle, the
+# sampled replicas of a 256-CU launch need 20 to 29 steps on the colouring and 28 to 39 on the CVRP)
+AT_SIZE_PARTIAL = {"colouring": 22, "cvrp_nearby": 30}
+AT_SIZE_SAMPLE = 16
+
+
+@pytest.mark.parametrize("name", list(AT_SIZE_PARTIAL))
+def test_vnd_at_size(oracle, name):
+    """The phase over several residencies (R = 2 * 32 * CUs + 37, the sample of tests/test_gpu_large_launch.py): sf_vnd_done_count reads
+    one word of each of R state rows, solve_vnd's launch loop ends on it, and a done replica leaves the step loop while its neighbours
+    in the wavefront's workgroup go on.  Every sampled replica is the stand-alone mirror run to done from the device state the
+    diverging search left, under the step seeds of random_seed + r."""
+    n_rep, u = _launch_size(False)
+    sample = _sample(n_rep, u, AT_SIZE_SAMPLE)
+    d = _start(name, n_rep)
+    mirrors = {r: _mirror(oracle, d, name, r) for r in sample}
+    scores = d.calculate_score()
+    assert all(tuple(scores[r].tolist()) == mirrors[r][1].current for r in sample)
+    assert d.vnd_done_count() == 0
+
+    def done_flags():
+        return sum(d.vnd_state(r)["done"] for r in range(n_rep))
+
+    c = d.solve_vnd(3, steps_per_launch=2)  # the step limit: 3 steps per replica end no descent here
+    assert c < n_rep and c == d.vnd_done_count() == done_flags(), c
+    c = d.solve_vnd(AT_SIZE_PARTIAL[name], steps_per_launch=8)  # some are done, the others still descend
+    assert 0 < c < n_rep and c == d.vnd_done_count() == done_flags(), c
+    assert d.solve_vnd(500, steps_per_launch=16) == n_rep and d.vnd_done_count() == n_rep == done_flags()
+    scores, best = d.calculate_score().copy(), d.best_scores().copy()
+    fresh = d.fresh_score()
+    assert (fresh == scores).all(), _rows_differ(fresh, scores)
+    snaps, steps = {}, []
+    for r in sample:
+        o, mirror = mirrors[r]
+        n = 0
+        while not mirror.done:
+            mirror.step()
+            n += 1
+        steps.append(n)
+        snap = snaps[r] = _snapshot(d, name, r)
+        assert snap[0] == list(mirror.current) and snap[1] == list(mirror.best_score) and snap[2] == vc.state_of(o, name), r
+        assert snap[3] == [mirror.stats[k] for k in vm.COUNTERS], (r, snap[3], mirror.stats)
+        assert snap[4] == mirror.state() and snap[4]["done"], (r, snap[4])
+        assert vm.is_local_optimum(vc.oracle_model(oracle, name, *snap[2]), vc.leaf_bits(name)), r
+    print(f"{name}: R={n_rep} sample={len(sample)} mirror steps {sorted(steps)}")
+    assert len(set(steps)) >= 3, steps  # the sampled descents end at different steps
+    d.solve_steps(5)  # all are done: nothing changes, not a counter
+    assert all(_snapshot(d, name, r) == snaps[r] for r in sample)
+    assert (d.calculate_score() == scores).all() and (d.best_scores() == best).all()
+    d.close()
 
 
 @pytest.mark.parametrize("name", ["cvrp_swap_first", "colouring"])
