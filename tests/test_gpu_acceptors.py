@@ -5,8 +5,9 @@ host-driven provider step.  The oracle cannot run these acceptors, so the tests 
 
 1. exact equivalences with the unchanged oracle: StepCounting(limit 0) is HillClimbing; GreatDeluge(rain_speed 0) is
    LateAcceptance(size > steps) -- both reduce to `sc >= initial`, because the step score never falls below the initial score under either;
-2. traced runs, candidate by candidate: every accept flag is the mirror's is_accepted(cur, sc), the acceptor state after every step is the
-   mirror's, an oracle model that follows by apply_move confirms the traced scores and doability.  The events that tell the rules apart
+2. traced runs, candidate by candidate: every accept flag is the mirror's is_accepted(cur, sc) (of the candidates that reach the acceptor: on
+   these models every doable one; trace_replica takes the predicate, tests/test_gpu_precedence_policies.py passes the precedence
+   engine's), the acceptor state after every step is the mirror's, an oracle model that follows by apply_move confirms the traced scores and doability.  The events that tell the rules apart
    (EVENTS) must all occur PER SITE, not per run: the water-level events belong to GreatDeluge and the count events to StepCounting, so no
    single run can hold all six; the three runs of a site (TRACE) together must, the GreatDeluge run holding its two and the FirstAccepted
    StepCounting run its two.  These runs follow replica 0; the two FirstAccepted runs are traced at replicas 1 and 2 as well, against a
@@ -197,11 +198,23 @@ def _acceptor_tuple(d, r):
     return tuple(level.tolist()), tuple(incr.tolist()), since
 
 
-def trace_replica(oracle, d, site, acceptor, param, replica, steps):
+def _doable(record, sc, cur):
+    """The default `consult` of trace_replica: every doable candidate reaches the acceptor."""
+    return True
+
+
+def trace_replica(oracle, d, site, acceptor, param, replica, steps, o=None, consult=_doable):
     """One replica of a context at the start of a phase under GreatDeluge / StepCounting, step by step through sf_solve_step_traced (the
     launch moves every replica one step).  The oracle model follows that replica by apply_move from the site's start state: its own
-    search code plays no part.  Returns {event: the first step that showed it}."""
-    o = _oracle_model(oracle, site)
+    search code plays no part.  o: the oracle model of the replica's working state (default: the site's start state; any list model on
+    class 0 or the site "scalar").  consult(record, sc, cur): does a DOABLE candidate reach the acceptor?  On the models of this file
+    every doable candidate does (the default); a move with Move::requires_score_improvement (the critical-path leaf's multi-swap,
+    evaluation.rs:95-113) is scored and counted and reaches the acceptor only when it beats the last step score
+    (tests/test_gpu_precedence_policies.py passes that predicate).  The accept flag is `doable and consult and mirror.is_accepted`.
+    Returns {event: the first step that showed it}; "gate_alone_refused": a doable candidate the acceptor on its own would have accepted
+    was kept from it by `consult`."""
+    if o is None:
+        o = _oracle_model(oracle, site)
     mirror = am.GreatDeluge(param) if acceptor == GD else am.StepCounting(param)
     cur = tuple(int(x) for x in o.score()[:2])
     assert tuple(d.calculate_score()[replica].tolist()) == cur
@@ -215,11 +228,17 @@ def trace_replica(oracle, d, site, acceptor, param, replica, steps):
         doable = (gf & 1) != 0
         assert (doable == (od != 0)).all(), step
         assert (gs[doable] == os_[doable][:, :2]).all(), step
-        for sc_row, fl in zip(gs, gf):
+        for rec, sc_row, fl in zip(gm, gs, gf):
             sc = tuple(int(x) for x in sc_row)
-            want = bool(fl & 1) and mirror.is_accepted(cur, sc)  # every doable candidate of these models reaches the acceptor
-            assert bool(fl & 2) == want, (step, sc, cur, mirror.state())
             if not fl & 1:
+                assert not fl & 2, step
+                continue
+            reaches = bool(consult(rec, sc, cur))
+            want = reaches and mirror.is_accepted(cur, sc)
+            assert bool(fl & 2) == want, (step, rec, sc, cur, mirror.state())
+            if not reaches:
+                if mirror.is_accepted(cur, sc):
+                    events.add("gate_alone_refused")
                 continue
             if acceptor == GD:
                 if want and not sc > cur:

@@ -164,7 +164,8 @@ def _configure(d, policy, forager, limit, acceptor=TABU, seed=SEED):
 
 def _tabu_tuple(d, r):
     st = d.tabu_state(r)
-    return (tuple(st["best"].tolist()) + (0, 0), tuple(st["pushes"]), st["entity"], st["value"], st["moves"], st["undo"])
+    best = tuple(st["best"].tolist())
+    return (best + (0,) * (4 - len(best)), tuple(st["pushes"]), st["entity"], st["value"], st["moves"], st["undo"])
 
 
 def _snapshot(d, site, replicas=range(R)):
@@ -194,16 +195,17 @@ def _signature(site, move, state):
     return tm.list_swap_signature(LIST_SCOPE[site], a, i, int(lists[a][i]), b, j, int(lists[b][j]))
 
 
-def trace_replica(oracle, d, site, policy, replica, steps, o=None):
+def trace_replica(oracle, d, site, policy, replica, steps, o=None, packer=None):
     """One replica of a context at the start of a phase under TabuSearch, step by step through sf_solve_step_traced (the launch moves
     every replica one step).  o: the oracle model of that replica's working state (default: the site's start state); it follows the
-    replica by apply_move, its own search plays no part.  The mirror starts fresh, as the phase does.  Returns {event: the first step
-    that showed it}."""
+    replica by apply_move, its own search plays no part.  The mirror starts fresh, as the phase does.  packer: the device packing of
+    a model of the site's shape and another size (default: the site's); the scores have the director's level count.  Returns {event:
+    the first step that showed it}."""
     if o is None:
         o = _oracle_model(oracle, site)
-    packer = PACKER[site]
+    packer, L = packer or PACKER[site], d.levels
     mirror = tm.TabuSearch(policy)
-    cur = tuple(int(x) for x in o.score()[:2])
+    cur = tuple(int(x) for x in o.score()[:L])
     assert tuple(d.calculate_score()[replica].tolist()) == cur
     assert _state(d, site, replica) == _oracle_state(o, site)
     mirror.phase_started(cur)
@@ -216,7 +218,7 @@ def trace_replica(oracle, d, site, policy, replica, steps, o=None):
         os_, od = o.evaluate_moves(gm)
         doable = (gf & 1) != 0
         assert (doable == (od != 0)).all(), step
-        assert (gs[doable] == os_[doable][:, :2]).all(), step
+        assert (gs[doable] == os_[doable][:, :L]).all(), step
         for mv, sc_row, fl in zip(gm, gs, gf):
             if not fl & 1:
                 assert not fl & 2, step  # a candidate that is not doable never reaches the acceptor
@@ -227,6 +229,8 @@ def trace_replica(oracle, d, site, policy, replica, steps, o=None):
             reasons, asp = mirror.tabu_reasons(sig), mirror.is_aspirational(sc)
             if not want:
                 refused_ids.add(sig.move_id)
+                for memory in reasons:  # (not in EVENTS: tests/test_gpu_precedence_policies.py asks for these of policies with several memories)
+                    events.add("refused_with_%s" % memory)
                 if len(reasons) == 1:
                     events.add("refused_by_%s_alone" % next(iter(reasons)))
                 if site == "scalar" and "value" in reasons and int(mv["kind"]) == 0 and int(mv["value"]) < 0:
@@ -250,7 +254,7 @@ def trace_replica(oracle, d, site, policy, replica, steps, o=None):
         else:
             events.add("step_applied_nothing")
             assert not (gf & 2).any()
-        cur = tuple(int(x) for x in o.score()[:2])
+        cur = tuple(int(x) for x in o.score()[:L])
         assert tuple(d.calculate_score()[replica].tolist()) == cur, (replica, step)
         mirror.step_ended(cur, applied_sig)
     assert _tabu_tuple(d, replica) == tm.packed_state(mirror, packer), replica
