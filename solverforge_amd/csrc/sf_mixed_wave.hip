@@ -471,7 +471,6 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
     // code ran there with a sixth of the lanes), only reads them.  Needs 32-bit deltas (ListModel::small32; the host passes ringd only then).
     int32_t* const ringd = (FAST && gl.ringd) ? gl.ringd + (size_t)r * GL * GRC * 2 : nullptr;
     const bool pre_eval = FAST && ringd != nullptr;
-    uint32_t prev_pulls = 0;  // pulls of the replica's previous step in this launch: long steps fill (and score) their rings in lumps of ~64 per leaf
     int64_t* s_load = (int64_t*)(mem + cv.load);
     uint32_t* s_off = (uint32_t*)(mem + cv.off);
     uint16_t* s_visits = (uint16_t*)(mem + cv.visits);
@@ -1097,7 +1096,6 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
             }
             lbv[0] = s1, lbv[1] = s2, lbv[2] = (int64_t)nk, lbv[3] = global_stat(sm, s1, s2, nk);
         }
-        uint32_t step_pulls = 0;  // pulls of this step (FAST: decides whether the next step fills its rings in lumps)
         uint64_t sidx, sseed;
         if (dry_run) {
             sidx = p.dry_step_index;
@@ -1476,7 +1474,6 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                 for (int l = 0; l < nl; ++l) live += ((exmask >> l) & 1u) ? 0u : 1u;
                 if (live > 1) fill_thr = (63u + live) / live + 8u;
             }
-            const bool lump_fill = prev_pulls >= 2048u;  // (a short step would throw most of a 64-entry lump away when it ends)
             for (int l = 0; l < nl; ++l) {
                 const int kind = lt.geti(l, LeafTab::KIND);
                 uint32_t* rq = ring + (size_t)l * GRC * 2;
@@ -1485,9 +1482,6 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                 const uint32_t hd_l = lt.get(l, LeafTab::HEAD);
                 const bool ex_l = ((exmask >> l) & 1u) != 0;
                 const uint32_t leaf_max_nearby = lt.get(l, LeafTab::MAXNB), leaf_min = lt.get(l, LeafTab::MINSZ), leaf_max = lt.get(l, LeafTab::MAXSZ);
-                // pre_eval + a long step: hysteresis -- a leaf is refilled when it runs below what the next replay batch needs, and then up to 64 pending
-                // (a generator call appends at most 64, the ring holds 128), so that the scoring stage below finds ~64 new entries of one kind at a time
-                const uint32_t fill_to = (pre_eval && lump_fill) ? (tl - hd_l < fill_thr ? 64u : 0u) : fill_thr;
                 if (pre_eval) lt.set(l, LeafTab::TAKEN, tl);  // (TAKEN is free between two replays) first entry the scoring stage has not seen
                 // LimitedMoveCursor around this leaf (limited.rs:14-94): the cursor answers `limit` pulls per step and never touches the inner
                 // cursor after that.  TAIL counts the candidates the leaf's cursor has answered since the step began (HEAD and TAIL restart at 0
@@ -1501,7 +1495,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
                     leaf_lim = uni(leaf_lim);
                     if (tl >= leaf_lim) g.done = 1;  // (a limit of 0 yields nothing)
                 }
-                while (!ex_l && !g.done && tl - hd_l < fill_to) {
+                while (!ex_l && !g.done && tl - hd_l < fill_thr) {
                     st_sources += 1;
                     bool keep = false;
                     uint32_t w0 = 0, w1 = 0, wx = 0;
@@ -3100,7 +3094,6 @@ __global__ __launch_bounds__(256, MODE == 1 ? (RUIN ? SF_MIXED_FAST_RUIN_BLOCKS_
             if (annealing) sa_step_ended(saw, p.sa, lane);
             wave_sync();
             st_steps += 1;
-            prev_pulls = step_pulls;
             la_cursor = la_cursor + 1 >= p.la_size ? 0 : la_cursor + 1;
         }
         PHS(7)
