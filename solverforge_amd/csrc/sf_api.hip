@@ -22,6 +22,7 @@
 #include "sf_kopt_tw.hip"
 #include "sf_precedence.hip"
 #include "sf_scalar_construct.h"
+#include "sf_mat_facts.h"  // mat16_symmetric: what holds of the compact matrix for the life of the context
 #include "sf_nbr_facts.h"  // NbrFacts / nbr_facts_rows: what holds of the neighbour index for the life of the context
 
 using namespace sf;
@@ -122,8 +123,9 @@ struct sf_ctx {
     ListModel lm_wave{};          // the list model as the COMPACT wave kernel sees it when the nodes are renumbered (ListModel::perm)
     NbrIndex nbr_wave{nullptr};   // ... and its neighbour index
     bool wave_renumbered = false;
+    int32_t mat16_sym = 0;        // the compact u16 matrix is symmetric word for word (sf_mat_facts.h; either numbering)
     int last_wave_mode = -1;      // launch mode of the last wave-engine launch (sf_list_wave_layout)
-    int32_t wave_spec_state = 0, wave_spec_reason = 0, wave_spec_key[22] = {};  // ... and whether it ran the kernel compiled for this context's constants (sf_debug_wave_spec)
+    int32_t wave_spec_state = 0, wave_spec_reason = 0, wave_spec_key[23] = {};  // ... and whether it ran the kernel compiled for this context's constants (sf_debug_wave_spec)
     int n_cus = 0;                // CUs of the device (read at the first wave launch)
     int32_t last_generic_flags = -1;  // what the last generic-engine launch took (sf_list_arith_flags)
     int32_t last_scalar_value_bytes = 0;  // value-type bytes of the last scalar-engine launch (sf_list_arith_flags)
@@ -1028,6 +1030,15 @@ static int build_list_model(sf_ctx* ctx, int d) {
                 m.mat16 = m16;
             }
         }
+    // the compact matrix's fact (sf_mat_facts.h), once: a host pass over the words as they come down.  A matrix past 64 MiB is not looked at
+    // (the fact stays "unknown", which offers nothing).
+    ctx->mat16_sym = 0;
+    if (m.mat16 && (size_t)m.dim * m.dim * 2 <= ((size_t)64 << 20)) {
+        std::vector<uint16_t> h16((size_t)m.dim * m.dim);
+        HIPCHK(ctx, hipMemcpyAsync(h16.data(), m.mat16, h16.size() * 2, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->mat16_sym = mat16_symmetric(h16.data(), m.dim);
+    }
     for (auto& kv : ctx->facts)
         if (kv.second.type == 1 && kv.second.d0 == (void*)m.mat) {
             m.mat_symmetric = kv.second.symmetric ? 1 : 0;
@@ -1291,7 +1302,7 @@ static int launch_list_wave(sf_ctx* ctx, const SearchParams& p, int n_replicas, 
     // the kernel compiled for this context's constants, when the policy wants it and it can be had; else the ahead-of-time one
     if (!ctx->n_cus) HIPCHK(ctx, hipDeviceGetAttribute(&ctx->n_cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
     const WaveSpecGate gate{pl.mode, q.move_budget != 0, (int32_t)std::min<int64_t>(std::max<int64_t>(q.n_steps, 0), INT32_MAX), n_replicas, pl.resident, ctx->n_cus, wave_spec_knob()};
-    const WaveSpecKey key = wave_spec_key(pl.levels, pl.wpe, *la.lm, q, ctx->nbr_facts, wave_spec_extras());
+    const WaveSpecKey key = wave_spec_key(pl.levels, pl.wpe, *la.lm, q, ctx->nbr_facts, ctx->mat16_sym, wave_spec_extras());
     ctx->wave_spec_state = SF_WSPEC_AOT, ctx->wave_spec_reason = wave_spec_wanted(gate);
     std::memcpy(ctx->wave_spec_key, &key, sizeof key);
     if (ctx->wave_spec_reason == SF_WSPEC_R_NONE) {
@@ -2424,11 +2435,12 @@ extern "C" int32_t sf_debug_wave_plan(const int32_t* shape, int32_t n_shape, con
 
 // The run-time specialisation of the wave engine (sf_wave_spec.h; tests/test_wave_spec.py, tests/test_gpu_wave_spec.py).
 // sf_debug_wave_spec: out[0] state of the context's last wave launch (0 ahead-of-time, 1 specialised, 2 fell back), out[1] its reason code
-// (SF_WSPEC_R_*), out[2] compiles of the process, out[3] the last compile's milliseconds (rounded up), out[4..] the key (WaveSpecKey: 22 words,
-// or its first 18 -- the key without the index's facts and their candidates).  `ctx` may be null: the process-wide figures alone.
+// (SF_WSPEC_R_*), out[2] compiles of the process, out[3] the last compile's milliseconds (rounded up), out[4..] the key's first 22 words
+// (WaveSpecKey up to `index_x`), or its first 18 -- the key without the index's facts and their candidates.  `ctx` may be null: the
+// process-wide figures alone.  (The words behind the 22nd: sf_debug_wave_spec_legs.)
 extern "C" int32_t sf_debug_wave_spec(const sf_ctx* ctx, int32_t* out, int32_t n_out) {
     static_assert(sizeof(WaveSpecKey) == sizeof(sf_ctx::wave_spec_key), "WaveSpecKey");
-    if (!out || (n_out != 4 + (int)(sizeof(WaveSpecKey) / 4) && n_out != 4 + SF_WSPEC_KEY_WORDS_V1)) return SF_ERR_INVALID;
+    if (!out || (n_out != 4 + SF_WSPEC_KEY_WORDS_V2 && n_out != 4 + SF_WSPEC_KEY_WORDS_V1)) return SF_ERR_INVALID;
     std::memset(out, 0, (size_t)n_out * 4);
     if (ctx) out[0] = ctx->wave_spec_state, out[1] = ctx->wave_spec_reason, std::memcpy(out + 4, ctx->wave_spec_key, (size_t)(n_out - 4) * 4);
     WaveSpecCache& c = wave_spec_cache();
@@ -2436,6 +2448,26 @@ extern "C" int32_t sf_debug_wave_spec(const sf_ctx* ctx, int32_t* out, int32_t n
     out[2] = c.compiles, out[3] = (int32_t)std::ceil(c.last_ms);
     return SF_OK;
 }
+// What the key of the context's last wave launch holds behind its 22nd word: out[0] = mat_sym, the compact matrix's symmetry as the
+// key carries it; out[1] = the leg candidates compiled in (SF_WSPEC_X_SYM_ROWS | SF_WSPEC_X_LEG_REAIM of `index_x`).
+extern "C" int32_t sf_debug_wave_spec_legs(const sf_ctx* ctx, int32_t* out, int32_t n_out) {
+    if (!ctx || !out || n_out != 2) return SF_ERR_INVALID;
+    WaveSpecKey k;
+    std::memcpy(&k, ctx->wave_spec_key, sizeof k);
+    out[0] = k.mat_sym, out[1] = k.index_x & SF_WSPEC_X_LEG_ALL;
+    return SF_OK;
+}
+// The compact matrix's fact for a host matrix of dim x dim 64-bit entries (sf_mat_facts.h; tests/test_mat_symmetry.py): the entries are
+// compressed by k_mat_compress16's rule and the reduction runs on the words.  out[0] = symmetric.  No device, no context.
+extern "C" int32_t sf_debug_mat_sym(const int64_t* mat, int32_t dim, int32_t* out, int32_t n_out) {
+    if (!mat || !out || dim < 1 || dim > 16384 || n_out != 1) return SF_ERR_INVALID;
+    std::vector<uint16_t> w((size_t)dim * dim);
+    for (size_t t = 0; t < w.size(); ++t) w[t] = mat16_word(mat[t]);
+    out[0] = mat16_symmetric(w.data(), dim);
+    return SF_OK;
+}
+// The leg candidates' gate: the SF_WSPEC_X_* bits a key whose matrix fact is `mat_sym` may compile in.
+extern "C" int32_t sf_debug_wave_spec_leg_gate(int32_t mat_sym) { return wave_spec_leg_allowed(mat_sym != 0); }
 // The LateAcceptance history of one replica as the search kernels keep it: out[n_slots][4] (n_slots = the configured history size) and the
 // cursor of the next step.  For parity tests of two kernels that must leave the same state behind.
 extern "C" int32_t sf_debug_late_acceptance(sf_ctx* ctx, int32_t replica, int64_t* out, int32_t n_slots, int32_t* cursor) {
@@ -2472,8 +2504,8 @@ extern "C" int32_t sf_debug_wave_spec_index_gate(const int32_t* in, int32_t n_in
 // file `out_path` (when given).  Returns the build's reason code (SF_WSPEC_R_NONE = compiled); `ms` receives the compile's milliseconds, `log`
 // the compiler's log.
 extern "C" int32_t sf_debug_wave_spec_compile(const int32_t* key, int32_t n_key, const char* arch, const char* out_path, char* opts, int32_t n_opts, char* log, int32_t n_log, double* ms) {
-    if (!key || (n_key * 4 != (int)sizeof(WaveSpecKey) && n_key != SF_WSPEC_KEY_WORDS_V1) || !arch) return SF_ERR_INVALID;
-    WaveSpecKey k{};  // (18 words: no facts of the index, none of their candidates)
+    if (!key || (n_key * 4 != (int)sizeof(WaveSpecKey) && n_key != SF_WSPEC_KEY_WORDS_V2 && n_key != SF_WSPEC_KEY_WORDS_V1) || !arch) return SF_ERR_INVALID;
+    WaveSpecKey k{};  // (18 words: no facts of the index, none of their candidates; 22: no fact of the matrix)
     std::memcpy(&k, key, (size_t)n_key * 4);
     if (!wave_spec_key_ok(k)) return SF_ERR_INVALID;
     const std::string csrc = wave_spec_csrc();

@@ -867,17 +867,38 @@ __device__ __forceinline__ void eval_generated_small(const ListModel& m, const L
     };
     // plus legs P0..P3, minus legs M0..M3: the table of eval_list_move_small
     const uint32_t p0 = leg(pa, chg ? na : vq);
+#ifdef SF_SPEC_SYM_ROWS  // the run-time unit, mat[a][b] == mat[b][a] for every pair: the two legs with a source-side endpoint, from its row
+    const uint32_t p1 = leg(ca ? x : na, chg ? pb : vq);
+    const uint32_t p2 = leg(x, chg ? vq : (adj ? nb : pb));
+#else
     const uint32_t p1 = leg(chg ? pb : vq, ca ? x : na);
     const uint32_t p2 = leg(ca ? x : pb, chg ? vq : (adj ? nb : x));
+#endif
+#ifdef SF_SPEC_LEG_REAIM  // the run-time unit: a leg the lane discards is aimed at m1's address, a line the lane fetches anyway
+    const uint32_t o_m1 = __umul24(x, dim4) + (adj ? vq : na) * (M16 ? 2u : 4u);
+    auto leg_at = [&](uint32_t byte_off) -> uint32_t {
+        if (M16) return *(const uint16_t*)((const char*)m.mat16 + byte_off);
+        return *(const uint32_t*)((const char*)m.mat32 + byte_off);
+    };
+    const uint32_t p3 = leg_at(ca ? o_m1 : __umul24(x, dim4) + nb * (M16 ? 2u : 4u));
+    const uint32_t m0 = leg(pa, x);
+    const uint32_t m1 = leg_at(o_m1);
+    const uint32_t m3 = leg_at(ca ? o_m1 : __umul24(vq, dim4) + nb * (M16 ? 2u : 4u));
+#else
     const uint32_t p3 = leg(x, nb);
     const uint32_t m0 = leg(pa, x);
     const uint32_t m1 = leg(x, adj ? vq : na);
     const uint32_t m3 = leg(vq, nb);
+#endif
     const uint32_t m2 = leg(adj ? vq : pb, adj ? nb : vq);
     int32_t d_cap = 0;
     if (lw.has_cap != 0u) {
         const int32_t dx = m.demand[x];
+#ifdef SF_SPEC_LEG_REAIM
+        const int32_t dyq = m.demand[(chg || intra) ? x : vq];  // (discarded below in exactly those lanes)
+#else
         const int32_t dyq = m.demand[vq];
+#endif
         const int32_t dy = chg ? 0 : dyq;
         const int32_t cap = KW ? lw.cap : (int32_t)m.capacity;
         const int32_t la0 = (int32_t)load[a] - cap, lb0 = (int32_t)load[b] - cap;

@@ -5,6 +5,7 @@
 //   -DSF_SPEC_WPE=4|5|6  waves per SIMD it is compiled for (launch mode 3 / 4 / 5)
 //   -DSF_SPEC_V(x)=.. -DSF_SPEC_DIM(x)=.. -DSF_SPEC_NCAP(x)=.. -DSF_SPEC_K0(x)=.. -DSF_SPEC_K1(x)=..
 //   -DSF_SPEC_NO_WIDE -DSF_SPEC_NO_TIES -DSF_SPEC_ROWS_FULL -DSF_SPEC_TIE_KEY -DSF_SPEC_RB=.. -DSF_SPEC_PB=..   facts of the neighbour index
+//   -DSF_SPEC_SYM_ROWS -DSF_SPEC_LEG_REAIM   the replay batch's leg gathers: source-side rows (a symmetric matrix), discarded gathers re-aimed
 #ifndef SF_SPEC_L
 #error "SF_SPEC_L: 2 or 4"
 #endif

@@ -30,11 +30,18 @@ struct WaveSpecKey {
     // of unknown facts and no such candidate.
     int32_t wide_ties, ties, rows_full;  // some equal-distance group has 64 members or more; some group has two; every row has min(dim, 64) finite entries
     int32_t index_x;
+    // A fact of the matrix the kernel gathers its legs from (sf_mat_facts.h), behind the twenty-two words above: a caller that hands
+    // over twenty-two names a matrix nobody has looked at.  The two leg candidates live in `index_x` with the index's.
+    int32_t mat_sym;  // mat[a][b] == mat[b][a] for every pair of the compact matrix, the not-finite word included
 };
+constexpr int32_t SF_WSPEC_KEY_WORDS_V2 = 22;  // the key before the matrix's fact: likewise
 constexpr int32_t SF_WSPEC_KEY_WORDS_V1 = 18;  // the key before the index's facts: still taken and handed out by the sf_debug_wave_spec* entry points
 enum { SF_WSPEC_X_MODEL = 1, SF_WSPEC_X_LA = 2, SF_WSPEC_X_LIMIT = 4, SF_WSPEC_X_PERM = 8, SF_WSPEC_X_EXPLICIT = 16, SF_WSPEC_X_ALL = 31 };
 // The candidates that rest on the index's facts: the next bits of SF_AMD_WAVE_SPEC_EXTRAS, kept in the key's `index_x`.
 enum { SF_WSPEC_X_NO_WIDE = 32, SF_WSPEC_X_TIE_KEY = 64, SF_WSPEC_X_NO_TIES = 128, SF_WSPEC_X_ROWS_FULL = 256, SF_WSPEC_X_INDEX_ALL = 480 };
+// The candidates of the replay batch's leg gathers, the next bits: two legs addressed by their source-side row (rests on the matrix's
+// symmetry), and the gathers a lane discards aimed at an address it fetches anyway (rests on nothing).
+enum { SF_WSPEC_X_SYM_ROWS = 512, SF_WSPEC_X_LEG_REAIM = 1024, SF_WSPEC_X_LEG_ALL = 1536 };
 // The candidates a launch compiles in unless SF_AMD_WAVE_SPEC_EXTRAS says otherwise: those that measured faster than the unit without them,
 // alone and on top of each other (profiles/wave_spec_ablation.txt).  The AcceptedCount limit lost 0.4 % alone and gained 0.2 % on
 // top of these three; the explicit seeds' absence lost 1.2 % alone and changed nothing on top: both stay arguments.
@@ -43,9 +50,13 @@ constexpr int32_t SF_WSPEC_X_DEFAULT = SF_WSPEC_X_MODEL | SF_WSPEC_X_LA | SF_WSP
 // word +2.0 %, full rows +4.7 %, each above the unit without it in every round and each above the pairs it joins; together +7.8 %.  "No
 // ties" is never offered for the benchmark's index (it has ties) and so was never measured: it stays a switch.
 constexpr int32_t SF_WSPEC_X_INDEX_DEFAULT = SF_WSPEC_X_NO_WIDE | SF_WSPEC_X_TIE_KEY | SF_WSPEC_X_ROWS_FULL;
+// Of the leg candidates (profiles/wave_legs_ablation.txt), on top of the six above: the source-side rows +3.9 % alone and +2.2 % on
+// top of the re-aimed gathers, above the unit without them in every run; the re-aimed gathers +0.7 % alone and -0.9 % on top of the source-side
+// rows, below the unit without them in every run: they stay a switch.
+constexpr int32_t SF_WSPEC_X_LEG_DEFAULT = SF_WSPEC_X_SYM_ROWS;
 static int32_t wave_spec_extras() {  // diagnostics (the ablation runs): read at every launch
     const char* e = std::getenv("SF_AMD_WAVE_SPEC_EXTRAS");
-    return e ? (std::atoi(e) & (SF_WSPEC_X_ALL | SF_WSPEC_X_INDEX_ALL)) : (SF_WSPEC_X_DEFAULT | SF_WSPEC_X_INDEX_DEFAULT);
+    return e ? (std::atoi(e) & (SF_WSPEC_X_ALL | SF_WSPEC_X_INDEX_ALL | SF_WSPEC_X_LEG_ALL)) : (SF_WSPEC_X_DEFAULT | SF_WSPEC_X_INDEX_DEFAULT | SF_WSPEC_X_LEG_DEFAULT);
 }
 
 // What the candidates' gate reads: the constants the packed word's width follows from, and the facts as the key's flags.
@@ -70,14 +81,19 @@ static int32_t wave_spec_index_allowed(const WaveSpecIndexGate& g) {
     if (g.rows_full && g.dim >= 32) a |= SF_WSPEC_X_ROWS_FULL;  // (the paired pass reads the first 32 entries of two rows)
     return a;
 }
+// Pure, beside it: the leg candidates a key of this matrix fact may compile in.  The source-side rows read mat[b][a] where the move's delta is
+// defined on mat[a][b]: never offered unless the two are the same word for every pair.
+static int32_t wave_spec_leg_allowed(int32_t mat_sym) { return SF_WSPEC_X_LEG_REAIM | (mat_sym ? SF_WSPEC_X_SYM_ROWS : 0); }
 // The key of a launch: the instantiation, the model as the kernel sees it, the launch's parameters, the index's facts; `extras` = the
 // candidates wanted (one whose value does not fit a literal of its type, or whose facts do not hold, is dropped).
 template <class Model, class Params>
-static WaveSpecKey wave_spec_key(int32_t levels, int32_t wpe, const Model& m, const Params& q, const NbrFacts& nf, int32_t extras) {
+static WaveSpecKey wave_spec_key(int32_t levels, int32_t wpe, const Model& m, const Params& q, const NbrFacts& nf, int32_t mat_sym, int32_t extras) {
     WaveSpecKey k{};
     k.levels = levels, k.wpe = wpe, k.V = m.V, k.dim = m.dim, k.n_cap = m.n_cap, k.k0 = q.leaf[0].max_nearby, k.k1 = q.leaf[1].max_nearby;
     k.wide_ties = nf.tie_max >= 64, k.ties = nf.tie_max >= 2, k.rows_full = nf.rows_full != 0;
     k.index_x = extras & SF_WSPEC_X_INDEX_ALL & wave_spec_index_allowed(WaveSpecIndexGate{k.V, k.dim, k.n_cap, k.wide_ties, k.ties, k.rows_full});
+    k.mat_sym = mat_sym != 0;
+    k.index_x |= extras & SF_WSPEC_X_LEG_ALL & wave_spec_leg_allowed(k.mat_sym);
     extras &= SF_WSPEC_X_ALL;
     auto fits = [](int64_t v) { return v >= INT32_MIN && v <= INT32_MAX; };
     if ((extras & SF_WSPEC_X_MODEL) && !(fits(m.capacity) && fits(m.cap_weight) && fits(m.dist_weight))) extras &= ~SF_WSPEC_X_MODEL;
@@ -158,6 +174,8 @@ static std::vector<std::string> wave_spec_options(const WaveSpecKey& k, const st
         for (auto& x : {word("SF_SPEC_TIE_KEY", 1), word("SF_SPEC_RB", wave_spec_rb(k.V)), word("SF_SPEC_PB", wave_spec_pb(k.n_cap))}) o.push_back(x);
     if (k.index_x & SF_WSPEC_X_NO_TIES) o.push_back(word("SF_SPEC_NO_TIES", 1));
     if (k.index_x & SF_WSPEC_X_ROWS_FULL) o.push_back(word("SF_SPEC_ROWS_FULL", 1));
+    if (k.index_x & SF_WSPEC_X_SYM_ROWS) o.push_back(word("SF_SPEC_SYM_ROWS", 1));
+    if (k.index_x & SF_WSPEC_X_LEG_REAIM) o.push_back(word("SF_SPEC_LEG_REAIM", 1));
     if (wave_spec_no_sym()) o.push_back("-DSF_WAVE_SYM=0");
     return o;
 }
@@ -168,7 +186,8 @@ static bool wave_spec_key_ok(const WaveSpecKey& k) {
     return (k.levels == 2 || k.levels == 4) && k.wpe >= 4 && k.wpe <= 6 && k.V >= 1 && k.dim >= 1 && k.n_cap >= 0 && k.k0 >= 1 && k.k1 >= 1 && (k.extras & ~SF_WSPEC_X_ALL) == 0 &&
            (!(k.extras & SF_WSPEC_X_LA) || k.la_size >= 1) && (!(k.extras & SF_WSPEC_X_LIMIT) || k.limit >= 1) &&
            (k.wide_ties | k.ties | k.rows_full | 1) == 1 && (!k.wide_ties || k.ties) &&
-           (k.index_x & ~wave_spec_index_allowed(WaveSpecIndexGate{k.V, k.dim, k.n_cap, k.wide_ties, k.ties, k.rows_full})) == 0;
+           (k.mat_sym | 1) == 1 &&
+           (k.index_x & ~(wave_spec_index_allowed(WaveSpecIndexGate{k.V, k.dim, k.n_cap, k.wide_ties, k.ties, k.rows_full}) | wave_spec_leg_allowed(k.mat_sym))) == 0;
 }
 
 // hiprtc through dlopen, by its versioned names.
